@@ -15,7 +15,13 @@ Phases, each W untimed warm-up steps then EXACTLY K timed steps between barrier 
      B(1+N) distinct items per step) -- the `catalogue` object.
 Rank 0 prints ONE JSON line.
 
-  python bench.py [--gpus N --steps K --warmup W]
+A plain run does what the headline figure needs and no more: set-up, the pass over every local user,
+phase 2 (W warm-up + K timed steps), the finite check of that phase, the line. `--full` adds phase 1,
+phase 3, the text and DCBR phases (--modes), AUC@val, the CPU baseline and the exact-f32 child run.
+`--dump-outputs DIR` writes what the headline phase's last timed step handed its caller as
+DIR/<name>.npy (float32); the inputs are seeded, so two builds can be compared output for output.
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 N>1 runs one process per GPU: under torch.distributed.run (RANK/WORLD_SIZE set) or, when started
 directly, bench.py launches the N ranks itself before touching any GPU.
 """
@@ -51,8 +57,16 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure too: the cold in-batch phase, the --modes "
+                         "phases, AUC@val, the CPU baseline and the exact-f32 comparison run. Without it only "
+                         "the steady-state in-batch phase runs (--modes and the --no-* switches are then moot)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps of the headline phase, write what its last step handed the "
+                         "caller (loss, scores, features, drawn negatives, dense parameters and gradients, "
+                         "user-table rows) as DIR/<name>.npy, float32")
     ap.add_argument("--modes", default="inbatch,catalogue,text,dcbr",
-                    help="comma list of phases after the cold one: inbatch (warm), catalogue, text "
+                    help="--full: comma list of phases after the cold one: inbatch (warm), catalogue, text "
                          "(config 4's mixed audio + text tower), dcbr (config 5)")
     ap.add_argument("--text-dim", type=int, default=256)
     ap.add_argument("--text-feature-dim", type=int, default=256, help="config 4: d = 256")
@@ -478,7 +492,7 @@ def exact_f32_probe(args):
     exact f32 MFMA (DCUE_CONV_F16=0 DCUE_WGRAD_F16=0 DCUE_DGRAD_F16=0; the library reads them at load,
     so in a child process, after this one's timed phases)."""
     env = dict(os.environ, DCUE_CONV_F16="0", DCUE_WGRAD_F16="0", DCUE_DGRAD_F16="0")
-    cmd = [sys.executable, os.path.abspath(__file__), "--modes", "inbatch,catalogue", "--no-eval",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--modes", "inbatch,catalogue", "--no-eval",
            "--no-cpu-baseline", "--no-f32-probe", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--users", str(args.users), "--tracks", str(args.tracks), "--interactions", str(args.interactions)]
     try:
@@ -574,7 +588,8 @@ def main():
     from dcrecommend.dcue.plan import TrainPlan
 
     B, N = args.batch, args.neg
-    modes = [m for m in args.modes.split(",") if m]
+    # a plain run: the headline phase alone (steady-state in-batch); everything else is --full's
+    modes = [m for m in args.modes.split(",") if m] if args.full else ["inbatch"]
     # users are sharded across ranks (row u of rank r = global user u*world + r): each rank owns its
     # users' embedding rows + Adam moments; the track table is replicated
     n_users_local = D.local_user_count(args.users, rank, world)
@@ -925,15 +940,51 @@ def main():
         mark("DCUE_BENCH_STALL_RANK: held before the first step")
         while True:
             time.sleep(1.0)
-    # ---- phase 1: in-batch, cold user table
+    def dump_outputs(plan, users_last, cap=1 << 20):
+        """--dump-outputs: what the phase's last timed step handed its caller, after the flush that
+        ends the timed region -- the plan's output views (loss, scores, user and item features at
+        the model's width, the drawn negatives), the dense parameters and gradients, and the user
+        table's rows for that step's users and for a fixed seeded sample of users. An array of more
+        than `cap` elements is written as a fixed seeded sample of them. float32 .npy files."""
+        net._sync_plan()
+        fl = net._flat
+        d, ds = args.feature_dim, nat.storage_dims(fl["dims"]).feature_dim
+        off = nat.workspace_outputs(fl["dims"], B, N, B)
+
+        def view(o, n, shape):
+            return plan.ws[o:o + 4 * n].view(torch.float32).view(shape)
+
+        table = net.user_embd.embeddings.weight.detach()
+        pick = torch.Generator().manual_seed(2718)
+        rows = torch.randperm(table.shape[0], generator=pick)[:2048].sort().values.to(dev)
+        arrays = {"loss": view(off[3], 1, (1,)), "scores": view(off[0], B * N, (B, N)),
+                  "user_features": view(off[1], B * ds, (B, ds))[:, :d],
+                  "item_features": view(off[2], B * ds, (B, ds))[:, :d],
+                  "negatives": plan.neg_item, "dense_parameters": fl["P"], "dense_gradients": fl["G"],
+                  "user_rows_last_batch": table[users_last], "user_rows_sample": table[rows]}
+        torch.cuda.synchronize()
+        if rank != 0:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, t in arrays.items():
+            a = t.detach().to(torch.float32).cpu().numpy()
+            if a.size > cap:
+                a = a.reshape(-1)[np.sort(np.random.RandomState(31).choice(a.size, cap, replace=False))]
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
     plan = make_plan(False)
-    ub, ib = batches(args.warmup + args.steps)
-    # (--gpu-only applies to the cold phase when that is the profiled one: its GPU-only timeline)
-    cold_gpu_only = args.gpu_only and args.profile_phase == "inbatch_cold"
-    dt, t_enq, gpu_ms_c, kern = timed_phase("inbatch_cold", plan, inbatch_step(ub, ib), gpu_only=cold_gpu_only)
-    out["inbatch_cold"] = summary(dt, t_enq, kern, B, 1, "inbatch", "inbatch_cold")
-    if gpu_ms_c is not None:
-        out["inbatch_cold"]["gpu_only_ms_per_step"] = gpu_ms_c
+    # ---- phase 1 (--full): in-batch, cold user table
+    cold_gpu_only = False
+    if args.full:
+        ub, ib = batches(args.warmup + args.steps)
+        # (--gpu-only applies to the cold phase when that is the profiled one: its GPU-only timeline)
+        cold_gpu_only = args.gpu_only and args.profile_phase == "inbatch_cold"
+        dt, t_enq, gpu_ms_c, kern = timed_phase("inbatch_cold", plan, inbatch_step(ub, ib), gpu_only=cold_gpu_only)
+        if args.dump_outputs and "inbatch" not in modes:  # the cold phase is then the headline
+            dump_outputs(plan, ub[-1])
+        out["inbatch_cold"] = summary(dt, t_enq, kern, B, 1, "inbatch", "inbatch_cold")
+        if gpu_ms_c is not None:
+            out["inbatch_cold"]["gpu_only_ms_per_step"] = gpu_ms_c
     # ---- phase 2: every local user once (outside any timed region), then in-batch steady state
     warm = inbatch_step(warm_users, warm_items)
     run(plan, warm, warm_users.shape[0])
@@ -941,6 +992,8 @@ def main():
         ub, ib = batches(args.warmup + args.steps)
         dt, t_enq, gpu_ms, kern = timed_phase("inbatch", plan, inbatch_step(ub, ib),
                                               gpu_only=args.gpu_only and not cold_gpu_only)
+        if args.dump_outputs:
+            dump_outputs(plan, ub[-1])
         out["inbatch"] = summary(dt, t_enq, kern, B, 1, "inbatch", "inbatch")
         if gpu_ms is not None:
             out["inbatch"]["gpu_only_ms_per_step"] = gpu_ms
@@ -1127,7 +1180,7 @@ def main():
             del all_u, all_t
         if not out["dcbr"]["finite"]:
             checks["failed"].append("dcbr: non-finite WRMF factors, regression parameters or loss")
-    head = out.get("inbatch", out["inbatch_cold"])
+    head = out["inbatch"] if "inbatch" in out else out["inbatch_cold"]
     E = args.user_embdim
     result = {
         "metric": "training triplets/sec (whole node) + AUC@val, DCUE d=128 at 1/2/4/8 MI355X",
@@ -1162,9 +1215,10 @@ def main():
                    "process_group_world": dist.get_world_size() if world > 1 else 1},
         "roofline": head["roofline"],
         "kernels": head["kernels"],
-        "inbatch_cold": {k: out["inbatch_cold"][k] for k in ("ms_per_step", "rows_per_s", "triplets_per_s",
-                                                             "host_enqueue_ms_per_step", "launches_per_step")},
     }
+    if "inbatch_cold" in out:
+        result["inbatch_cold"] = {k: out["inbatch_cold"][k] for k in ("ms_per_step", "rows_per_s", "triplets_per_s",
+                                                                      "host_enqueue_ms_per_step", "launches_per_step")}
     if host_trace:
         result["host_issue_us"] = host_trace
     if "allreduce_ms_per_step" in head:
@@ -1204,15 +1258,15 @@ def main():
         result["replica_fingerprint_min_max"] = [lo, hi]
     if world > 1:
         D.broadcast_buffers_(net)  # DDP semantics: evaluate with rank 0's BN statistics
-    if rank == 0 and not args.no_eval:
+    if rank == 0 and args.full and not args.no_eval:
         # AUC@val of the trained model (outside the timed region): DCUE.score over an eval_pct
         # sample of this rank's users (nn/dcue.py:380-449, 580-603) on the GPU evaluator
         ev = evaluate_val(args, net, tracks, pair_user, pair_track, split, n_users_local, dev)
         result["auc_val"] = ev.pop("auc")
         result["eval"] = ev
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, n_users_local)
-    if rank == 0 and world == 1 and not args.no_f32_probe:
+    if rank == 0 and world == 1 and args.full and not args.no_f32_probe:
         result["exact_f32"] = exact_f32_probe(args)
     if rank == 0:
         print(json.dumps(result), flush=True)

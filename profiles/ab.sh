@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for r in $(seq 1 $ROUNDS); do
   for V in A B; do
     E=$([ $V = A ] && echo "$A" || echo "$B")
-    env $E timeout -k 10 200 python3 $ROOT/bench.py --no-cpu-baseline --no-eval --steps 200 --warmup 20 \
+    env $E timeout -k 10 200 python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 200 --warmup 20 \
       --modes $MODES > "$OUT/${V}_$r.log" 2>&1 || exit 1
     python3 - "$OUT/${V}_$r.log" "$V" "$E" <<'PY' >> "$OUT/summary.txt"
 import json, sys

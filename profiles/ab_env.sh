@@ -13,7 +13,7 @@ for r in $(seq 1 $ROUNDS); do
   for E in "$@"; do
     i=$((i + 1))
     EV=$([ "$E" = "-" ] && echo "DCUE_AB_VARIANT=$i" || echo "$E")
-    env $EV timeout -k 10 200 python3 $ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
+    env $EV timeout -k 10 200 python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps ${STEPS:-20} --warmup ${WARMUP:-5} \
       --modes $MODES ${BENCH_EXTRA:-} > "$OUT/v${i}_$r.log" 2>&1 || exit 1
     python3 - "$OUT/v${i}_$r.log" "$EV" <<'PY' >> "$OUT/summary.txt"
 import json, sys

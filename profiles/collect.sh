@@ -20,7 +20,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
-BENCH="$ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps $STEPS --warmup $WARMUP"
+BENCH="$ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps $STEPS --warmup $WARMUP"
 (cd "$ROOT" && timeout -k 10 300 python3 $BENCH > "$OUT/plain.log" 2>&1)
 grep '^{' "$OUT/plain.log" | tail -n 1 > "$OUT/${TAG}_bench_plain.json"
 for PH in inbatch catalogue inbatch_cold text; do
@@ -30,7 +30,7 @@ done
 for PH in inbatch catalogue text; do
   for C in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 180 rocprofv3 --pmc $C --kernel-include-regex 'k_conv1_wgrad|k_conv_wgrad16|k_emb_flush_rows|k_conv_rows|k_text_fwd|spin_kernel' \
-      -f csv -d "$OUT/pmc_${PH}_$C" -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-eval --steps 40 \
+      -f csv -d "$OUT/pmc_${PH}_$C" -o run -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 40 \
       --warmup 5 --profile-phase $PH > "$OUT/pmc_${PH}_$C.log" 2>&1
   done
 done

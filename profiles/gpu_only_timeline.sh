@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/gpuonly_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 200 rocprofv3 --kernel-trace -f csv -d "$OUT/trace" -o run -- python3 $ROOT/bench.py \
+timeout -k 10 200 rocprofv3 --kernel-trace -f csv -d "$OUT/trace" -o run -- python3 $ROOT/bench.py --full \
   --no-cpu-baseline --no-eval --no-f32-probe --steps ${STEPS:-8} --warmup 3 --modes inbatch --gpu-only \
   --profile-phase ${PHASE:-inbatch} \
   > "$OUT/prof.log" 2>&1 || exit 1

@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/kab_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 MODES=$([ "$PHASE" = catalogue ] && echo catalogue || ([ "$PHASE" = text ] && echo text || echo inbatch))
-BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps 20 --warmup 5 --modes $MODES --profile-phase $PHASE"
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps 20 --warmup 5 --modes $MODES --profile-phase $PHASE"
 i=0
 for E in "$@"; do
   i=$((i + 1))

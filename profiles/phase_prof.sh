@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/stats_$PH" -o run \
-  -- python3 $ROOT/bench.py --no-cpu-baseline --no-eval --steps $STEPS --warmup 10 --profile-phase $PH "$@" \
+  -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps $STEPS --warmup 10 --profile-phase $PH "$@" \
   > "$OUT/stats_$PH.log" 2>&1
 python3 "$ROOT/profiles/phase_kernels.py" "$OUT/stats_$PH" 40 > "$OUT/${TAG}_${PH}_kernels.txt"
 cat "$OUT/${TAG}_${PH}_kernels.txt"

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 MODES=$([ "$PH" = catalogue ] && echo catalogue || echo inbatch)
 COUNTERS=${PMC_COUNTERS:-SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS GRBM_GUI_ACTIVE}
 timeout -s KILL 240 rocprofv3 --pmc $COUNTERS \
-  -f csv -d "$OUT/raw" -o run -- python3 $ROOT/bench.py --no-cpu-baseline --no-eval --steps 20 --warmup 5 \
+  -f csv -d "$OUT/raw" -o run -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 20 --warmup 5 \
   --modes $MODES --profile-phase $PH > "$OUT/run.log" 2>&1 || exit 1
 python3 - "$OUT" > "$OUT/summary.txt" <<'PY'
 import csv, glob, os, sys, collections

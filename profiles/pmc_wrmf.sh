@@ -15,7 +15,7 @@ i=0
 for C in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE" FETCH_SIZE WRITE_SIZE; do
   i=$((i + 1))
   timeout -s KILL 240 rocprofv3 --pmc $C --kernel-include-regex 'k_wrmf' -f csv -d "$OUT/p$i" -o run \
-    -- python3 $ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps 5 --warmup 2 --modes dcbr \
+    -- python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps 5 --warmup 2 --modes dcbr \
     > "$OUT/p$i.log" 2>&1 || exit 1
 done
 python3 - "$OUT" "$TAG" "$OUT" <<'PY'

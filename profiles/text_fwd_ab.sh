@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/textab_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps 20 --warmup 5 --modes text --profile-phase text"
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps 20 --warmup 5 --modes text --profile-phase text"
 i=0
 for E in "$@"; do
   i=$((i + 1))

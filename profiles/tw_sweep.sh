@@ -11,9 +11,9 @@ cd /tmp && export TMPDIR=/tmp
 MODES=$([ "$PH" = catalogue ] && echo catalogue || echo inbatch)
 for TW in "$@"; do
   export DCUE_ROWS_TW=$TW
-  timeout -k 10 200 python3 $ROOT/bench.py --no-cpu-baseline --no-eval --steps 60 --warmup 10 --modes $MODES \
+  timeout -k 10 200 python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --steps 60 --warmup 10 --modes $MODES \
     > "$OUT/plain_$TW.log" 2>&1 || exit 1
-  timeout -k 10 200 rocprofv3 --kernel-trace -f csv -d "$OUT/trace_$TW" -o run -- python3 $ROOT/bench.py \
+  timeout -k 10 200 rocprofv3 --kernel-trace -f csv -d "$OUT/trace_$TW" -o run -- python3 $ROOT/bench.py --full \
     --no-cpu-baseline --no-eval --steps 30 --warmup 5 --modes $MODES --profile-phase $PH > "$OUT/prof_$TW.log" 2>&1 || exit 1
   python3 $ROOT/profiles/phase_kernels.py "$OUT/trace_$TW" 14 > "$OUT/kernels_$TW.txt"
   python3 $ROOT/profiles/timeline.py "$OUT/trace_$TW" "k_conv_rows<0, 0," > "$OUT/timeline_$TW.txt" 2>&1

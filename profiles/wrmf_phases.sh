@@ -10,7 +10,7 @@ i=0
 for E in "$@"; do
   i=$((i + 1))
   EV=$([ "$E" = "-" ] && echo "DCUE_AB_VARIANT=$i" || echo "$E")
-  env $EV timeout -k 10 300 python3 $ROOT/bench.py --no-cpu-baseline --no-eval --no-f32-probe --steps 2 --warmup 1 \
+  env $EV timeout -k 10 300 python3 $ROOT/bench.py --full --no-cpu-baseline --no-eval --no-f32-probe --steps 2 --warmup 1 \
     --modes dcbr > "$OUT/v$i.log" 2>&1; [ $? -ge 124 ] && exit 1
   python3 - "$OUT/v$i.log" "$EV" >> "$OUT/summary.txt" <<'PY'
 import json, sys

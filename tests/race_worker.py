@@ -94,7 +94,9 @@ def main():
     tower = sys.argv[1] if len(sys.argv) > 1 else "bn"
     sites = sys.argv[2].split(",") if len(sys.argv) > 2 else ["wgrad_2", "dgrad_2"]
     us = int(sys.argv[3]) if len(sys.argv) > 3 else 5000
-    base = run(tower)
+    # the run to compare with: a file the parent saved (its own undelayed run), else this process's.
+    # Under DCUE_LEGACY_ORDERS=1 this process's undelayed run is racy too, so the parent supplies one
+    base = torch.load(sys.argv[4]) if len(sys.argv) > 4 else run(tower)
     res = {"legacy_orders": os.environ.get("DCUE_LEGACY_ORDERS", "0"), "base_finite": finite(base)}
     for site in sites:
         r = run(tower, {site: us}, check="probe")

@@ -154,18 +154,43 @@ SMALL = ["--steps", "3", "--warmup", "1", "--no-eval", "--no-cpu-baseline", "--u
 def test_bench_single_gpu_line():
     """The bench line's contract fields at a small workload: the steady-state in-batch value, the
     cold in-batch and the catalogue phases, kernel rooflines with the step-level fraction."""
-    r = _bench(SMALL)
+    r = _bench(["--full"] + SMALL)
     assert r["n_gpus"] == 1 and r["value"] > 0 and r["unit"] == "triplets/s"
     assert r["catalogue"]["rows_per_s"] > 0 and r["inbatch_cold"]["rows_per_s"] > 0
     assert 0 < r["roofline"]["step_frac"] < 1
     assert r["kernels"] and all(k["avg_ms"] > 0 for k in r["kernels"])
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times the steady-state in-batch phase alone -- no cold, catalogue, text
+    or DCBR phase, no AUC, CPU baseline or f32 child run -- for exactly --steps steps, keeps that
+    phase's finite check, and --dump-outputs leaves the last timed step's outputs as float32 .npy
+    files whose loss is the one the line's check read."""
+    import numpy as np
+    small = ["--steps", "3", "--warmup", "1", "--users", "3000", "--tracks", "4000", "--interactions", "60000"]
+    r = _bench(small + ["--dump-outputs", str(tmp_path / "out")])
+    assert r["steps"] == 3 and r["value"] > 0 and r["unit"] == "triplets/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 64 * 20 / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+    for k in ("inbatch_cold", "catalogue", "text", "dcbr", "eval", "cpu_baseline", "exact_f32"):
+        assert k not in r, k
+    assert r["auc_val"] is None
+    assert r["checks"]["after"] == ["inbatch"] and r["checks"]["failed"] == [] and r["checks"]["finite"]
+    got = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert set(got) == {"loss", "scores", "user_features", "item_features", "negatives", "dense_parameters",
+                        "dense_gradients", "user_rows_last_batch", "user_rows_sample"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["scores"].shape == (64, 20) and got["item_features"].shape == (64, 128)
+    assert got["user_rows_last_batch"].shape == (64, 300) and got["user_rows_sample"].shape == (2048, 300)
+    assert float(got["loss"][0]) == r["checks"]["last_loss_inbatch"]
+    assert np.abs(got["dense_gradients"]).max() > 0 and np.abs(got["scores"]).max() > 0
+
+
 def test_bench_launches_its_own_ranks():
     """`bench.py --gpus 2` started directly (no torch.distributed.run) spawns two ranks before any
     GPU call; here both share the one GPU over gloo with the Python exchange (RCCL needs a GPU per
     rank); rank 0 prints the single line with the whole-job numbers."""
-    r = _bench(["--gpus", "2"] + SMALL, env={"DCUE_DIST_BACKEND": "gloo"})
+    r = _bench(["--gpus", "2", "--full"] + SMALL, env={"DCUE_DIST_BACKEND": "gloo"})
     assert r["n_gpus"] == 2 and r["config"]["process_group_world"] == 2
     assert r["config"]["global_batch"] == 2 * r["config"]["batch_per_gpu"]
     assert r["value"] > 0 and r["catalogue"]["rows_per_s"] > 0

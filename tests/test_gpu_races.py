@@ -81,14 +81,23 @@ def test_poisoned_scratch_and_probes():
     assert W.finite(rt)
 
 
-def test_legacy_orders_fail():
+def test_legacy_orders_fail(tmp_path):
     """The detector has teeth: with round 4's orders (DCUE_LEGACY_ORDERS=1) a delayed layer-2 weight
     gradient and a delayed conv-2 input gradient both change the run; the probes name the first
-    kernel that went non-finite."""
+    kernel that went non-finite.
+
+    The run they are compared with is the undelayed one under the current orders, made here and
+    handed to the child as a file. Round 4's orders are racy by construction, so the child's own
+    undelayed run cannot serve: now and then it goes non-finite by itself,
+    which failed this test's precondition on a run where nothing was wrong."""
+    import race_worker as W
+    base = W.run("bn")
+    assert W.finite(base)
+    torch.save({k: base[k] for k in ("loss", "P", "emb")}, str(tmp_path / "base.pt"))
     env = dict(os.environ, DCUE_LEGACY_ORDERS="1")
     p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tests", "race_worker.py"), "bn",
-                        "wgrad_2,dgrad_2", str(DELAY_US)], env=env, stdout=subprocess.PIPE,
-                       stderr=subprocess.STDOUT, text=True, timeout=100)
+                        "wgrad_2,dgrad_2", str(DELAY_US), str(tmp_path / "base.pt")], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=100)
     assert p.returncode == 0, p.stdout[-3000:]
     res = json.loads(p.stdout.strip().splitlines()[-1])
     print(res)
