@@ -4,6 +4,7 @@ The reference's dense embedding gradient makes torch.optim.Adam step every user 
 (nn/dcue.py:143-147,209). NativeAdam(defer_embedding=True) performs the zero-gradient steps of rows
 outside the batch later, replaying the recorded per-step scalars through the same fp32 operations.
 Bar: BIT-EXACT -- after any flush every parameter, buffer and Adam moment equals the dense run's.
+Frozen rows (freeze, refresh, return, thaw, checkpoint) are tested in tests/test_gpu_frozen.py.
 """
 import pytest
 import torch
