@@ -547,6 +547,12 @@ bool on_side_worker();
 // inputs (capi.hip)
 bool late_wait_at_conv1();
 
+// ------------------------------------------------------------- ranking / top-K (rank.hip, topk.hip)
+// factor rows are normalised into rows of DP = d rounded up to 16 floats (the MFMA k split)
+__host__ __device__ constexpr int rank_dp(int d) { return (d + 15) & ~15; }
+// k_rank_normalize: y[r] = x[rows ? rows[r] : r] / max(||.||, 1e-8), zero-padded to dp
+int launch_rank_normalize(const float* x, const int32_t* rows, int64_t n, int d, int dp, float* y, hipStream_t s);
+
 // ---------------------------------------------------------------- diagnostics (debug.hip)
 // a spin kernel ahead of the work at `site` when a delay is set for it (dcue_debug_delay)
 int debug_delay(int site, hipStream_t s);

@@ -27,8 +27,6 @@ constexpr int kRankCap = 4096;    // positives (within the lists) per query
 constexpr int kRankTile = 64;     // queries x candidates per scoring workgroup
 constexpr int kRankChunk = 8192;  // candidates per histogram workgroup
 
-__host__ __device__ constexpr int rank_dp(int d) { return (d + 15) & ~15; }
-
 // one wave per row: y = x / max(||x||_2, eps), zero padding to DP (rows[] may gather)
 __global__ __launch_bounds__(256) void k_rank_normalize(const float* __restrict__ x, const int32_t* rows,
                                                         int64_t n, int d, int dp, float* __restrict__ y) {
@@ -43,6 +41,12 @@ __global__ __launch_bounds__(256) void k_rank_normalize(const float* __restrict_
   const float nrm = fmaxf(sqrtf(ss), 1e-8f);
   float* yr = y + r * dp;
   for (int k = lane; k < dp; k += 64) yr[k] = k < d ? xr[k] / nrm : 0.f;
+}
+
+int launch_rank_normalize(const float* x, const int32_t* rows, int64_t n, int d, int dp, float* y, hipStream_t s) {
+  DCUE_LAUNCH(k_rank_normalize, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, rows, n, d, dp, y);
+  DCUE_LAUNCH_CHECK();
+  return DCUE_OK;
 }
 
 // S[q][c] for q < nq, c < nc. Wave w owns candidate columns 16w..16w+15 of the tile and all four

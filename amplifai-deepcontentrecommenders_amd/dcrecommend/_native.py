@@ -105,10 +105,11 @@ class PlanConfig(ctypes.Structure):
 
 MT_STATE_BYTES = 624 * 4 + 16
 MAX_LOG_CAP = 256
-ABI_VERSION = 16
+ABI_VERSION = 17
 COMM_F32, COMM_U64 = 0, 1  # dcue_host_allreduce_fn dtypes
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32)
 RANK_SPLIT, RANK_SINGLE = 0, 1
+TOPK_MAX_K = 128  # DCUE_TOPK_MAX_K
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd")
@@ -184,6 +185,11 @@ _SIGS = {
                                    ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_rank_metrics": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, _P,
                            _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_topk_workspace_bytes": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                   ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_topk": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P,
+                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P],
+                  ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_debug_delay": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "dcue_debug_probes": ([_P], ctypes.c_int),

@@ -528,6 +528,69 @@ class DCUE(Trainer):
             s = self.model.sim(q.unsqueeze(0).expand_as(rows), rows)
         return s.cpu().numpy().tolist(), [float(t) for t in targets]
 
+    # ------------------------------------------------------------------ recommendation
+    def _require_factors(self):
+        if self.user_factors is None or self.item_factors is None or self._item_meta is None:
+            raise RuntimeError("no factors to recommend from: fit the model (or call _user_factors / "
+                               "_item_factors, or load a checkpoint and bind its item dataset) first")
+
+    def _index_source(self, ds):
+        """Whose user / item indices name the factor rows: every dataset of one triplets frame
+        shares them (the category codes over all triplets)."""
+        return ds if ds is not None else self.train_data if self.train_data is not None else self._tracks_src
+
+    def _topk(self, kind, ds, exclude_seen):
+        """rank.TopK per (kind, dataset, exclude_seen), cached as _evaluator caches its lists."""
+        key = ("topk", kind, id(ds), bool(exclude_seen))
+        if key not in self._evals:
+            mask = (self._item_meta >= 0).astype(np.uint8)  # items without audio have zero factors
+            if ds is not None:
+                split = np.zeros_like(mask)
+                split[ds.split_items()] = 1
+                mask &= split
+            if kind == "song":
+                ptr, idx = rank.identity_csr(len(mask))
+            elif exclude_seen:
+                src = ds if ds is not None else self.train_data
+                if src is None:
+                    raise RuntimeError("exclude_seen needs the interactions: pass dataset= (any split's "
+                                       "dataset holds the all-split matrix) or fit() first")
+                ptr, idx = src.user_item_csr()
+            else:
+                ptr = idx = None
+            self._evals[key] = rank.TopK(ptr, idx, mask, self.device)
+        return self._evals[key]
+
+    def _as_pairs(self, ds, idx, score, count):
+        names = self._index_source(ds).itemindex2songid
+        return [[(names[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
+                for r in range(len(count))]
+
+    def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True):
+        """The k best songs for each user id, by the cosine of DCUE.score: one list per user of
+        (song_id, score) pairs, best first (as_ids=False: the raw (idx [n, k], score [n, k],
+        count [n]) arrays over item indices). Candidates are the dataset's (or loader's) split songs,
+        or every song with audio; exclude_seen drops the songs the user interacted with in any
+        split -- the "seen" set of the evaluator's negatives. One fused GPU pass
+        (include/dcue.h dcue_topk) for all users; the reference has only predict(), one user and one
+        Python candidate list at a time. An unknown user id raises KeyError."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        index = self._index_source(ds).user_index
+        rows = np.array([index[u] for u in users], dtype=np.int64)
+        out = self._topk("user", ds, exclude_seen).topk(self.user_factors, self._item_feat_by_index(), rows, k)
+        return self._as_pairs(ds, *out) if as_ids else out
+
+    def similar_songs(self, songs, k=10, dataset=None):
+        """The k songs most similar to each song id (item-to-item on the same kernel: the item factors
+        on both sides, each song excluded from its own list); same return as recommend()."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        index = self._index_source(ds).item_index
+        rows = np.array([index[s] for s in songs], dtype=np.int64)
+        feat = self._item_feat_by_index()
+        return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
+
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):
         """nn/dcue.py:580-603."""
         if split == 'train':

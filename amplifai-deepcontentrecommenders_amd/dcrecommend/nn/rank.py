@@ -5,6 +5,9 @@ The reference scores one user at a time: it builds a pandas frame of every split
 calls model.sim and sklearn's roc_auc_score / average_precision_score. Here the candidate lists
 are two bitmasks over the catalogue plus the all-split interaction CSR, built once per dataset on
 the host, and every sampled query is ranked on the GPU in one call.
+
+TopK (dcue_topk) is the serving counterpart: the k best candidates per query, with a candidate mask
+and a per-query exclusion CSR, fused so that the score matrix is never written.
 """
 import numpy as np
 import torch
@@ -129,3 +132,99 @@ class RankEvaluator:
         if not (np.all((auc[sane] >= 0.0) & (auc[sane] <= 1.0)) and np.all((ap[sane] >= 0.0) & (ap[sane] <= 1.0))):
             raise RuntimeError("dcue_rank_metrics: AUC / AP outside [0, 1]")
         return auc, ap, ok
+
+
+def identity_csr(n):
+    """Each row excludes itself (DCUE.similar_songs: a song is not its own neighbour)."""
+    return np.arange(n + 1, dtype=np.int64), np.arange(n, dtype=np.int32)
+
+
+class TopK:
+    """Device-resident exclusion lists and candidate mask of one recommendation setting and the
+    grow-only workspace of dcue_topk -- RankEvaluator's counterpart for "the k best candidates".
+
+    excl_ptr [n_query_rows + 1] int64 / excl_idx int32: per query row, the sorted candidates never to
+    return (both None: no exclusion); cand_mask [n_cand] uint8 (None: every candidate; then n_cand
+    must be given)."""
+
+    DEFAULT_QUERY_BATCH = 4096
+
+    def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None):
+        self.device = torch.device(device)
+        if (excl_ptr is None) != (excl_idx is None):
+            raise ValueError("excl_ptr and excl_idx go together")
+        self.excl_ptr = self.excl_idx = None
+        if excl_ptr is not None:
+            self.excl_ptr = torch.from_numpy(np.ascontiguousarray(excl_ptr, dtype=np.int64)).to(self.device)
+            idx = np.ascontiguousarray(excl_idx, dtype=np.int32)
+            self.excl_idx = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(self.device)
+        self.cand_mask = None
+        if cand_mask is not None:
+            self.cand_mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(self.device)
+            n_cand = int(self.cand_mask.numel())
+        if n_cand is None:
+            raise ValueError("n_cand is needed without a candidate mask")
+        self.n_cand = int(n_cand)
+        self._ws = None
+
+    def workspace_bytes(self, d, qb, k, cand_split=0):
+        import ctypes
+        nbytes = ctypes.c_size_t()
+        nat.check(nat.lib().dcue_topk_workspace_bytes(self.n_cand, d, qb, k, cand_split, ctypes.byref(nbytes)),
+                  "dcue_topk_workspace_bytes")
+        return nbytes.value
+
+    def _workspace(self, d, qb, k, cand_split):
+        nbytes = self.workspace_bytes(d, qb, k, cand_split)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
+        """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
+        as dcue_topk writes them (no non-finite check)."""
+        nat.require_gpu(query_feat, "query_feat")
+        nat.require_gpu(cand_feat, "cand_feat")
+        query_feat = query_feat.contiguous().float()
+        cand_feat = cand_feat.contiguous().float()
+        if cand_feat.shape[0] != self.n_cand or cand_feat.shape[1] != query_feat.shape[1]:
+            raise ValueError("candidate factors %s do not match %d candidates / d=%d"
+                             % (tuple(cand_feat.shape), self.n_cand, query_feat.shape[1]))
+        if self.excl_ptr is not None and query_feat.shape[0] + 1 != self.excl_ptr.numel():
+            raise ValueError("query factors have %d rows, the CSR %d" % (query_feat.shape[0],
+                                                                          self.excl_ptr.numel() - 1))
+        k = int(k)
+        if not 1 <= k <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, k))
+        q = torch.as_tensor(np.asarray(queries, dtype=np.int32)).to(self.device)
+        nq = int(q.numel())
+        idx = torch.full((max(nq, 1), k), -1, dtype=torch.int32, device=self.device)
+        score = torch.full((max(nq, 1), k), float("-inf"), dtype=torch.float32, device=self.device)
+        count = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.device)
+        flags = torch.zeros(max(nq, 1), dtype=torch.int32, device=self.device)
+        if nq:
+            if int(q.min()) < 0 or int(q.max()) >= query_feat.shape[0]:
+                raise IndexError("query index out of range")
+            d = int(query_feat.shape[1])
+            qb = int(min(nq, self.DEFAULT_QUERY_BATCH if query_batch is None else query_batch))
+            ws = self._workspace(d, qb, k, int(cand_split))
+            nat.check(nat.lib().dcue_topk(
+                nat.ptr(query_feat), query_feat.shape[0], nat.ptr(cand_feat), self.n_cand, d, nat.ptr(q), nq,
+                nat.ptr(self.excl_ptr), nat.ptr(self.excl_idx), nat.ptr(self.cand_mask), k, qb, int(cand_split),
+                nat.ptr(ws), ws.numel(), nat.ptr(idx), nat.ptr(score), nat.ptr(count), nat.ptr(flags),
+                nat.stream_handle(self.device)), "dcue_topk")
+        return idx[:nq], score[:nq], count[:nq], flags[:nq]
+
+    def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
+        """(idx int64 [n, k], score float32 [n, k], count int32 [n]) numpy arrays, best first; rows
+        with fewer than k eligible candidates end in idx -1 / score -inf.
+
+        Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
+        infinite: a diverged model fails here as it fails in DCUE.score."""
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split)
+        flags = flags.cpu().numpy()
+        bad = (flags & 2).astype(bool)
+        if bad.any():
+            raise ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
+                             "finite)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+        return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define DCUE_ABI_VERSION 16
+#define DCUE_ABI_VERSION 17
 #define DCUE_N_MELS 128
 #define DCUE_N_FRAMES 131
 #define DCUE_N_BN 6
@@ -554,6 +554,40 @@ int dcue_rank_metrics(const float* query_feat, int64_t n_query_rows, const float
 /* DCUE._item_factors' averaging (nn/dcue.py:655-668): f <- (f + f + ... n_iter times) / n_iter in
  * fp32, for 131-frame tracks whose n_iter eval passes are identical (no random crop). */
 int dcue_factor_repeat_mean(float* f, int64_t n, int32_t n_iter, void* stream);
+
+/* ------------------------------------------------------------------- top-K recommendation (ABI 17) */
+/* The k best candidates of each query by nn.CosineSimilarity(dim=1), without the score matrix:
+ * what a recommender serves ("the K tracks for this user"; item-to-item with the item factors on
+ * both sides). Scores are dcue_rank_metrics' -- the same normalisation (x / max(||x||, 1e-8)) and the
+ * same exact-f32 MFMA summation order, which depends on d alone -- so the lists do not depend on
+ * query_batch or cand_split, bit for bit.
+ *   query_feat [n_query_rows][d], cand_feat [n_cand][d], queries[n_queries]: as dcue_rank_metrics
+ *     (repeats allowed). d <= 256, else DCUE_ERR_UNSUPPORTED.
+ *   excl_ptr[n_query_rows+1], excl_idx: CSR over query rows of candidates never to return for the
+ *     query (what the user already played), each row sorted, no repeats; both null: no exclusion.
+ *   cand_mask[n_cand]: 0 = never return the candidate; null: every candidate.
+ *   Candidate c is eligible for a query when its mask byte is non-zero, it is not in the query's
+ *     exclusion row and its score is not NaN. Order: score descending, then index ascending.
+ *   out_idx / out_score [n_queries][k], best first; where fewer than k candidates are eligible the
+ *     tail is idx -1 / score -inf, and out_count[q] says how many entries are real.
+ *   out_flags[q] bit 1: an eligible candidate's score is NaN or infinite (non-finite factors: a
+ *     diverged model). A NaN is never returned; +-inf order as ordinary values.
+ *   1 <= k <= DCUE_TOPK_MAX_K. query_batch queries are ranked per pass. cand_split: candidate chunks a
+ *     query tile is divided over, each leaving k partial keys that a merge kernel combines -- 0: the
+ *     library chooses (enough workgroups to fill the chip); positive: forced (at most 32, and at most
+ *     one per 64 candidates).
+ *   Workspace: both sides' normalised rows and the partial keys, (queries of a pass) x cand_split x
+ *     k x 8 bytes -- never a [query_batch][n_cand] buffer. dcue_topk_workspace_bytes is a host
+ *     computation, and dcue_topk validates every argument on the host before its first device call.
+ * Synchronises `stream` before returning. */
+#define DCUE_TOPK_MAX_K 128
+int dcue_topk_workspace_bytes(int64_t n_cand, int32_t d, int32_t query_batch, int32_t k,
+                              int32_t cand_split, size_t* bytes_host);
+int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_feat, int64_t n_cand,
+              int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
+              const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k, int32_t query_batch,
+              int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
+              int32_t* out_count, int32_t* out_flags, void* stream);
 
 #ifdef __cplusplus
 }

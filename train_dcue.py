@@ -6,6 +6,7 @@ this is that driver for the MI355X build:
 
   python train_dcue.py --triplets triplets.csv --metadata metadata.csv --save-dir models/
   python train_dcue.py --synthetic --num-epochs 1 --save-dir /tmp/dcue   # self-contained demo
+  python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv      # + each user's top 10
 
 triplets: (user_id, song_id, score) by column position (datasets/dcuedataset.py:229,238);
 metadata: song_id in column 1 and a `data_mel` column of torch.save'd [128, T] tensors
@@ -49,7 +50,13 @@ def parse(argv=None):
     ap.add_argument("--eval-pct", type=float, default=0.025)
     ap.add_argument("--val-pct", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument("--recommend-k", type=int, default=0,
+                    help="after training, the K best unseen songs of every training user (0: off)")
+    ap.add_argument("--recommend-out", help="CSV for --recommend-k: user_id, rank, song_id, score")
+    args = ap.parse_args(argv)
+    if (args.recommend_k > 0) != bool(args.recommend_out):
+        ap.error("--recommend-k and --recommend-out go together")
+    return args
 
 
 def synthetic_data(n_users, n_tracks, n_pairs, out_dir, seed):
@@ -106,7 +113,18 @@ def main(argv=None):
                 val_pct=args.val_pct, optimize=args.optimize, model_type=args.model_type)
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
+    if args.recommend_k > 0 and args.recommend_out:
+        write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out)
     return dcue
+
+
+def write_recommendations(dcue, users, k, path):
+    """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank)."""
+    if dcue.best_user_factors is not None:
+        dcue.insert_best_factors()
+    lists = dcue.recommend(users, k=k)
+    rows = [(u, r + 1, song, score) for u, lst in zip(users, lists) for r, (song, score) in enumerate(lst)]
+    pd.DataFrame(rows, columns=["user_id", "rank", "song_id", "score"]).to_csv(path, index=False)
 
 
 if __name__ == "__main__":
