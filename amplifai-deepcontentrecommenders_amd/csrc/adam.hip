@@ -505,7 +505,7 @@ int launch_emb_flush_rows(const dcue_model* md, int step, hipStream_t s) {
 
 
 
-static AdamScalars form_scalars(const dcue_adam_args* a);
+AdamScalars form_scalars(const dcue_adam_args* a);
 // Step t for the rows that have a gradient (emb_rows from the backward); records step t's scalars.
 __global__ __launch_bounds__(256) void k_adam_touched(float* __restrict__ p, float* __restrict__ m,
                                                       float* __restrict__ v,
@@ -820,7 +820,7 @@ int launch_emb_flush(const dcue_model* md, hipStream_t s) {
 
 // host scalars as torch.optim.Adam forms them from Python floats (double), each rounded once to
 // float where the CPU kernel takes it as a float scalar
-static AdamScalars form_scalars(const dcue_adam_args* a) {
+AdamScalars form_scalars(const dcue_adam_args* a) {
   const double bc1 = 1.0 - pow(a->beta1, (double)a->step);
   const double bc2 = 1.0 - pow(a->beta2, (double)a->step);
   const double w = 1.0 - a->beta1;

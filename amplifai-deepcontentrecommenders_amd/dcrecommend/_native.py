@@ -103,6 +103,16 @@ class PlanConfig(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("mt", ctypes.c_void_p)]
 
 
+class FoldinConfig(ctypes.Structure):
+    """dcue_foldin_config (fold-in of unseen users, added under ABI 17)."""
+    _fields_ = [("steps", ctypes.c_int32), ("n_neg", ctypes.c_int32), ("max_pos", ctypes.c_int32),
+                ("margin", ctypes.c_float), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("weight_decay", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+
+FOLDIN_MAX_STEPS, FOLDIN_MAX_NEG, FOLDIN_MAX_POS = 4096, 256, 1024
+FOLDIN_EMPTY, FOLDIN_NONFINITE, FOLDIN_DROPPED = 1, 2, 4  # out_flags bits
 MT_STATE_BYTES = 624 * 4 + 16
 MAX_LOG_CAP = 256
 ABI_VERSION = 17
@@ -191,6 +201,12 @@ _SIGS = {
                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P],
                   ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
+    "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                     ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_user_foldin": ([ctypes.POINTER(Model), _P, ctypes.c_int64, _P, _P, _P, ctypes.c_int32, ctypes.c_int64,
+                          ctypes.POINTER(FoldinConfig), _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_foldin_negatives": ([ctypes.c_int64, _P, _P, _P, ctypes.c_int32, ctypes.c_int64,
+                               ctypes.POINTER(FoldinConfig), ctypes.c_int32, _P, _P], ctypes.c_int),
     "dcue_debug_delay": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "dcue_debug_probes": ([_P], ctypes.c_int),
     "dcue_debug_probe_count": ([], ctypes.c_int),

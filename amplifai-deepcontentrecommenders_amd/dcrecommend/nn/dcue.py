@@ -591,6 +591,85 @@ class DCUE(Trainer):
         feat = self._item_feat_by_index()
         return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
 
+    # ------------------------------------------------------------------ unseen users
+    def _cand_mask(self, ds):
+        """The candidates of _topk: songs with audio (the others have zero factors), in the split."""
+        mask = (self._item_meta >= 0).astype(np.uint8)
+        if ds is not None:
+            split = np.zeros_like(mask)
+            split[ds.split_items()] = 1
+            mask &= split
+        return mask
+
+    def _history_items(self, histories, ds):
+        """(usable, full): per history the item indices with audio, and all of them. An unknown song
+        id raises KeyError, a history without a usable song ValueError."""
+        index = self._index_source(ds).item_index
+        usable, full = [], []
+        for h, songs in enumerate(histories):
+            items = sorted({int(index[s]) for s in songs})
+            full.append(items)
+            usable.append([i for i in items if self._item_meta[i] >= 0])
+            if not usable[-1]:
+                raise ValueError("history %d has no song with audio: nothing to fold in from" % h)
+        return usable, full
+
+    def fold_in(self, histories, steps=30, n_neg=None, lr=None, max_pos=64, seed=0, dataset=None, init=None):
+        """User factors [n, feature_dim] (device) for users outside the trained table -- a new
+        listener, a playlist, a session -- each given as a list of song ids. With the model frozen,
+        one fresh embedding row per history is learned against the trained towers with the training
+        loss itself (cosine hinge, n_neg sampled negatives per positive, Adam on that row only; margin,
+        betas and eps are the trainer's, n_neg defaults to neg_batch_size and lr to the trainer's): all
+        steps of all users in one kernel launch (include/dcue.h dcue_user_foldin). The reference has no
+        counterpart: its predict() looks the user up in user_index.
+
+        init [n, u_embdim]: the rows' starting values; default N(0, 1) rows from a CPU torch.Generator
+        seeded with `seed` (nn.Embedding's distribution). Songs without audio are dropped from the
+        positives. An unknown song id raises KeyError, a history with no usable song ValueError."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        usable, _ = self._history_items(histories, ds)
+        return self._fold_in(usable, ds, steps, n_neg, lr, max_pos, seed, init)[1]
+
+    def _fold_in(self, usable, ds, steps, n_neg, lr, max_pos, seed, init):
+        self.model._require_device()
+        n = len(usable)
+        if init is None:
+            gen = torch.Generator().manual_seed(int(seed))
+            init = torch.randn(n, self.u_embdim, generator=gen)
+        init = torch.as_tensor(init, dtype=torch.float32).to(self.device)
+        key = ("foldin", id(ds))
+        if key not in self._evals:
+            self._evals[key] = rank.FoldIn(self._cand_mask(ds), self.device)
+        cfg = rank.FoldIn.config(steps, self.neg_batch_size if n_neg is None else n_neg, max_pos, self.margin,
+                                 self.lr if lr is None else lr, self.beta_one, self.beta_two, self.eps, 0.0, seed)
+        ptr, idx = rank.histories_csr(usable)
+        emb, feat, loss, _, flags = self._evals[key].fold_in_raw(self.model._model_struct(),
+                                                                 self._item_feat_by_index(), ptr, idx, init, cfg)
+        bad = (flags.cpu().numpy() & nat.FOLDIN_NONFINITE).astype(bool)
+        if bad.any():
+            raise ValueError("Input contains NaN. (fold-in of history %d: the loss or the factor is not "
+                             "finite)" % int(np.argmax(bad)))
+        return emb, feat, loss
+
+    def recommend_for(self, histories, k=10, dataset=None, exclude_history=True, as_ids=True, **fold_in_kwargs):
+        """recommend() for users outside the trained table: fold_in(histories, **fold_in_kwargs), then
+        the fused top-k pass with each history as the user's exclusion list (every song of it, with
+        or without audio). Returns what recommend() returns."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        usable, full = self._history_items(histories, ds)
+        args = dict(steps=30, n_neg=None, lr=None, max_pos=64, seed=0, init=None)
+        unknown = set(fold_in_kwargs) - set(args)
+        if unknown:
+            raise TypeError("recommend_for() got unexpected fold_in arguments %s" % sorted(unknown))
+        args.update(fold_in_kwargs)
+        feat = self._fold_in(usable, ds, **args)[1]
+        ptr, idx = rank.histories_csr(full) if exclude_history else (None, None)
+        out = rank.TopK(ptr, idx, self._cand_mask(ds), self.device).topk(
+            feat, self._item_feat_by_index(), np.arange(len(full)), k)
+        return self._as_pairs(ds, *out) if as_ids else out
+
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):
         """nn/dcue.py:580-603."""
         if split == 'train':

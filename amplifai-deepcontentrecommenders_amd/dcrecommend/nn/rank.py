@@ -8,6 +8,9 @@ the host, and every sampled query is ranked on the GPU in one call.
 
 TopK (dcue_topk) is the serving counterpart: the k best candidates per query, with a candidate mask
 and a per-query exclusion CSR, fused so that the score matrix is never written.
+
+FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
+learned against the frozen towers, all steps in one kernel launch.
 """
 import numpy as np
 import torch
@@ -228,3 +231,121 @@ class TopK:
             raise ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
                              "finite)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
         return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
+
+
+def histories_csr(rows):
+    """int64 pointers / int32 indices of per-row candidate lists, each sorted and without repeats
+    (dcue_topk's exclusion CSR, dcue_user_foldin's history CSR)."""
+    ptr = np.zeros(len(rows) + 1, dtype=np.int64)
+    idx = []
+    for r, row in enumerate(rows):
+        idx.append(np.unique(np.asarray(row, dtype=np.int64)).astype(np.int32))
+        ptr[r + 1] = ptr[r] + len(idx[-1])
+    return ptr, (np.concatenate(idx) if idx else np.zeros(0, np.int32)).astype(np.int32)
+
+
+class FoldIn:
+    """Device-resident candidate mask and the grow-only workspace of dcue_user_foldin -- TopK's
+    counterpart for users outside the trained table: one fresh embedding row per user, learned
+    against the frozen towers in one kernel launch for all steps (include/dcue.h).
+
+    cand_mask [n_cand] uint8: the candidates negatives are drawn from (None: every candidate; then
+    n_cand must be given)."""
+
+    DEFAULT_USER_BATCH = 4096
+
+    def __init__(self, cand_mask, device, n_cand=None):
+        self.device = torch.device(device)
+        self.cand_mask = None
+        if cand_mask is not None:
+            self.cand_mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(self.device)
+            n_cand = int(self.cand_mask.numel())
+        if n_cand is None:
+            raise ValueError("n_cand is needed without a candidate mask")
+        self.n_cand = int(n_cand)
+        self._ws = None
+
+    def workspace_bytes(self, dims, n_users, max_pos, n_neg):
+        import ctypes
+        nbytes = ctypes.c_size_t()
+        nat.check(nat.lib().dcue_foldin_workspace_bytes(ctypes.byref(dims), self.n_cand, n_users, max_pos, n_neg,
+                                                        ctypes.byref(nbytes)), "dcue_foldin_workspace_bytes")
+        return nbytes.value
+
+    def _workspace(self, dims, n_users, max_pos, n_neg):
+        nbytes = self.workspace_bytes(dims, n_users, max_pos, n_neg)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _csr(self, hist_ptr, hist_idx):
+        ptr = torch.from_numpy(np.ascontiguousarray(hist_ptr, dtype=np.int64)).to(self.device)
+        idx = np.ascontiguousarray(hist_idx, dtype=np.int32)
+        if len(idx) and (idx.min() < 0 or idx.max() >= self.n_cand):
+            raise IndexError("history index out of range")
+        return ptr, torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(self.device)
+
+    @staticmethod
+    def config(steps, n_neg, max_pos, margin, lr, beta1, beta2, eps, weight_decay=0.0, seed=0):
+        if not 0 <= int(steps) <= nat.FOLDIN_MAX_STEPS:
+            raise ValueError("steps must be in 0..%d, got %d" % (nat.FOLDIN_MAX_STEPS, steps))
+        if not 1 <= int(n_neg) <= nat.FOLDIN_MAX_NEG:
+            raise ValueError("n_neg must be in 1..%d, got %d" % (nat.FOLDIN_MAX_NEG, n_neg))
+        if not 1 <= int(max_pos) <= nat.FOLDIN_MAX_POS:
+            raise ValueError("max_pos must be in 1..%d, got %d" % (nat.FOLDIN_MAX_POS, max_pos))
+        return nat.FoldinConfig(int(steps), int(n_neg), int(max_pos), float(margin), float(lr), float(beta1),
+                                float(beta2), float(eps), float(weight_decay), int(seed) & (2 ** 64 - 1))
+
+    def fold_in_raw(self, model, cand_feat, hist_ptr, hist_idx, init, cfg, user_batch=None, row0=0,
+                    want_grad=False):
+        """(emb [n, E], feat [n, d], loss [n, steps], grad [n, E] or None, flags int32 [n]) device
+        tensors, as dcue_user_foldin writes them. model: the nat.Model struct of the frozen towers;
+        init [n, E]: the rows' starting values (not modified); hist_ptr / hist_idx: the histories of
+        rows row0 .. row0 + n - 1 at those positions of the CSR. Users are passed user_batch at a time
+        with their global row, so the result does not depend on user_batch."""
+        import ctypes
+        nat.require_gpu(cand_feat, "cand_feat")
+        nat.require_gpu(init, "init")
+        cand_feat = cand_feat.contiguous().float()
+        d, E = int(model.dims.feature_dim), int(model.dims.user_embdim)
+        if cand_feat.shape[0] != self.n_cand or cand_feat.shape[1] != d:
+            raise ValueError("candidate factors %s do not match %d candidates / d=%d"
+                             % (tuple(cand_feat.shape), self.n_cand, d))
+        n = int(init.shape[0])
+        if init.dim() != 2 or init.shape[1] != E:
+            raise ValueError("init must be [n, %d], got %s" % (E, tuple(init.shape)))
+        if len(hist_ptr) < row0 + n + 1:
+            raise ValueError("the history CSR has %d rows, %d are needed" % (len(hist_ptr) - 1, row0 + n))
+        ptr, idx = self._csr(hist_ptr, hist_idx)
+        emb = init.detach().clone().contiguous().float()
+        steps = int(cfg.steps)
+        feat = torch.zeros((max(n, 1), d), dtype=torch.float32, device=self.device)
+        loss = torch.zeros((max(n, 1), max(steps, 1)), dtype=torch.float32, device=self.device)
+        grad = torch.zeros((max(n, 1), E), dtype=torch.float32, device=self.device) if want_grad else None
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        ub = int(min(max(n, 1), self.DEFAULT_USER_BATCH if user_batch is None else user_batch))
+        if ub < 1:
+            raise ValueError("user_batch must be positive")
+        ws = self._workspace(model.dims, ub, int(cfg.max_pos), int(cfg.n_neg))
+        for u0 in range(0, n, ub):
+            nu = min(ub, n - u0)
+            nat.check(nat.lib().dcue_user_foldin(
+                ctypes.byref(model), nat.ptr(cand_feat), self.n_cand, nat.ptr(self.cand_mask), nat.ptr(ptr),
+                nat.ptr(idx), nu, row0 + u0, ctypes.byref(cfg), ctypes.c_void_p(emb[u0:].data_ptr()), nat.ptr(ws),
+                ws.numel(), ctypes.c_void_p(feat[u0:].data_ptr()),
+                ctypes.c_void_p(loss[u0:].data_ptr()) if steps else None,
+                ctypes.c_void_p(grad[u0:].data_ptr()) if grad is not None else None,
+                ctypes.c_void_p(flags[u0:].data_ptr()), nat.stream_handle(self.device)), "dcue_user_foldin")
+        return emb[:n], feat[:n], loss[:n, :steps], (grad[:n] if grad is not None else None), flags[:n]
+
+    def negatives(self, hist_ptr, hist_idx, n, cfg, step, row0=0):
+        """int32 [n, max_pos, n_neg] device tensor: the negatives dcue_user_foldin draws at `step` for
+        rows row0 .. row0 + n - 1 (-1: a dropped slot, or a positive slot the history does not fill)."""
+        import ctypes
+        ptr, idx = self._csr(hist_ptr, hist_idx)
+        out = torch.full((max(n, 1), int(cfg.max_pos), int(cfg.n_neg)), -1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().dcue_foldin_negatives(self.n_cand, nat.ptr(self.cand_mask), nat.ptr(ptr), nat.ptr(idx),
+                                                  int(n), int(row0), ctypes.byref(cfg), int(step), nat.ptr(out),
+                                                  nat.stream_handle(self.device)), "dcue_foldin_negatives")
+        torch.cuda.synchronize(self.device)  # (ptr / idx are temporaries of this call)
+        return out[:n]

@@ -589,6 +589,70 @@ int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_f
               int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
               int32_t* out_count, int32_t* out_flags, void* stream);
 
+/* ------------------------------------------------------ fold-in of unseen users (added under ABI 17) */
+/* A user outside the trained table -- a new listener, a playlist, a session -- gets a factor without
+ * retraining: with the model frozen, one fresh embedding row per new user is learned against the
+ * trained towers with the training loss itself (cosine hinge, n_neg sampled negatives per positive)
+ * and torch.optim.Adam steps on that row alone. All `steps` steps of every user run in ONE kernel
+ * launch (a workgroup keeps 16 users from the first step to the last); the reference has no
+ * counterpart (its predict() looks the user up in user_index).
+ *   m: read only, and only the user tower's segments of m->params (user_embd.linear1 / linear2).
+ *     Nothing in *m is written: not params, not emb, not the moments, not the deferred log.
+ *   cand_feat [n_cand][d] (d = dims.feature_dim), cand_mask[n_cand] (nullable: every candidate is
+ *     eligible as a negative): dcue_topk's operands.
+ *   hist_ptr / hist_idx: dcue_topk's exclusion CSR format (int64 pointers, int32 candidate indices,
+ *     ascending and distinct per row), indexed by GLOBAL row r = row0 + local row, so a caller that
+ *     chunks its users passes the same arrays to every chunk and to dcue_topk. emb, out_feat,
+ *     out_loss, out_grad and out_flags are indexed by the local row 0 .. n_users-1.
+ * Semantics. H = row r's history, P = min(|H|, max_pos), t = 0 .. steps-1:
+ *   1. Positives of step t: H[(t * max_pos + i) mod |H|], i < P (a rotating window; the whole
+ *      history when it fits).
+ *   2. Negative (r, t, i, j), j < n_neg: mix(z) is the splitmix64 finaliser (z ^= z >> 30;
+ *      z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31);
+ *      z0 = mix(seed + 0x9E3779B97F4A7C15 * (r + 1)); for attempt a = 0..7:
+ *      x = mix(z0 ^ (t << 40 | i << 24 | j << 8 | a)), c = ((x >> 32) * n_cand) >> 32; the first c with
+ *      cand_mask[c] != 0 that is not in H (binary search) is the negative. All eight rejected: the
+ *      slot contributes nothing and flag bit 2 is set. Draws depend on r, not on the call's batching.
+ *   3. Forward: uf = W2 relu(W1 relu(e) + b1) + b2 (userembedding.py:33-44); cos(uf, f) with both
+ *      sides normalised (x / max(||x||, 1e-8)) before the dot product, as the trainer's score;
+ *      loss_t = (1/P) sum_i sum_j max(0, margin - (cos(uf, f_pos_i) - cos(uf, f_neg_ij))), the value
+ *      BEFORE the step's update, into out_loss[row][t]. An exact tie passes half the gradient.
+ *   4. Backward to e only. out_grad (nullable) receives the last executed step's gradient, before
+ *      its Adam step.
+ *   5. Adam on the row: step count t + 1, scalars formed as dcue_adam_step forms them, constant lr,
+ *      moments starting at +0; the trainer's element update (bit-identical to it for the gradient
+ *      the kernel produced).
+ *   6. out_feat [n_users][d] = tower(final e); with steps == 0 the tower of the initial row.
+ *   7. An empty history leaves the row untouched, its losses 0 and sets flag bit 0. A non-finite
+ *      loss or factor (or a history entry outside [0, n_cand)) sets bit 1.
+ * Workspace: the normalised candidates, the per-step Adam scalars and, for E beyond about 400, the tiles'
+ * activations (at most 5 x 16 x (E + 20) floats per 16 users) -- nothing of size n_users x n_cand, no
+ * gathered factor rows. dcue_foldin_workspace_bytes is a host computation; dcue_user_foldin
+ * validates every argument on the host before its first device call (DCUE_ERR_INVALID: a null
+ * required pointer, steps / n_neg / max_pos out of range, n_cand <= 0; DCUE_ERR_UNSUPPORTED:
+ * d > 256 or E > 1024; DCUE_ERR_WORKSPACE; n_users == 0 is DCUE_OK) and synchronises `stream`
+ * before returning.
+ * dcue_foldin_negatives: the sampler alone for `step`, out_neg [n_users][max_pos][n_neg] candidate
+ * indices, -1 = a dropped slot or i >= P. Asynchronous on `stream`. */
+typedef struct dcue_foldin_config {
+  int32_t steps;   /* 0..4096 */
+  int32_t n_neg;   /* 1..256 */
+  int32_t max_pos; /* 1..1024 */
+  float margin;
+  double lr, beta1, beta2, eps, weight_decay; /* as dcue_adam_args */
+  uint64_t seed;
+} dcue_foldin_config;
+int dcue_foldin_workspace_bytes(const dcue_dims* dims, int64_t n_cand, int32_t n_users,
+                                int32_t max_pos, int32_t n_neg, size_t* bytes_host);
+int dcue_user_foldin(const dcue_model* m, const float* cand_feat, int64_t n_cand,
+                     const uint8_t* cand_mask, const int64_t* hist_ptr, const int32_t* hist_idx,
+                     int32_t n_users, int64_t row0, const dcue_foldin_config* cfg, float* emb,
+                     void* ws, size_t ws_bytes, float* out_feat, float* out_loss, float* out_grad,
+                     int32_t* out_flags, void* stream);
+int dcue_foldin_negatives(int64_t n_cand, const uint8_t* cand_mask, const int64_t* hist_ptr,
+                          const int32_t* hist_idx, int32_t n_users, int64_t row0,
+                          const dcue_foldin_config* cfg, int32_t step, int32_t* out_neg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ this is that driver for the MI355X build:
   python train_dcue.py --triplets triplets.csv --metadata metadata.csv --save-dir models/
   python train_dcue.py --synthetic --num-epochs 1 --save-dir /tmp/dcue   # self-contained demo
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv      # + each user's top 10
+  python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-for new.csv
+                                                  # the top 10 of users outside the training set
 
 triplets: (user_id, song_id, score) by column position (datasets/dcuedataset.py:229,238);
 metadata: song_id in column 1 and a `data_mel` column of torch.save'd [128, T] tensors
@@ -53,9 +55,15 @@ def parse(argv=None):
     ap.add_argument("--recommend-k", type=int, default=0,
                     help="after training, the K best unseen songs of every training user (0: off)")
     ap.add_argument("--recommend-out", help="CSV for --recommend-k: user_id, rank, song_id, score")
+    ap.add_argument("--recommend-for", metavar="FILE.csv",
+                    help="columns user_id,song_id: histories of users outside the training set; their "
+                         "lists (DCUE.recommend_for: fold-in, then top K) are written instead of the "
+                         "training users'")
     args = ap.parse_args(argv)
     if (args.recommend_k > 0) != bool(args.recommend_out):
         ap.error("--recommend-k and --recommend-out go together")
+    if args.recommend_for and not args.recommend_out:
+        ap.error("--recommend-for needs --recommend-k and --recommend-out")
     return args
 
 
@@ -114,15 +122,25 @@ def main(argv=None):
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
     if args.recommend_k > 0 and args.recommend_out:
-        write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out)
+        if args.recommend_for:
+            new = pd.read_csv(args.recommend_for, dtype=str)
+            histories = {u: list(g) for u, g in new.groupby("user_id", sort=False)["song_id"]}
+            write_recommendations(dcue, list(histories), args.recommend_k, args.recommend_out,
+                                  histories=histories, seed=args.seed)
+        else:
+            write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out)
     return dcue
 
 
-def write_recommendations(dcue, users, k, path):
-    """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank)."""
+def write_recommendations(dcue, users, k, path, histories=None, seed=0):
+    """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank).
+    histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
-    lists = dcue.recommend(users, k=k)
+    if histories is not None:
+        lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed)
+    else:
+        lists = dcue.recommend(users, k=k)
     rows = [(u, r + 1, song, score) for u, lst in zip(users, lists) for r, (song, score) in enumerate(lst)]
     pd.DataFrame(rows, columns=["user_id", "rank", "song_id", "score"]).to_csv(path, index=False)
 
