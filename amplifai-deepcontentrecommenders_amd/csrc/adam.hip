@@ -503,9 +503,6 @@ int launch_emb_flush_rows(const dcue_model* md, int step, hipStream_t s) {
   return timer_end(&tsc);
 }
 
-
-
-AdamScalars form_scalars(const dcue_adam_args* a);
 // Step t for the rows that have a gradient (emb_rows from the backward); records step t's scalars.
 __global__ __launch_bounds__(256) void k_adam_touched(float* __restrict__ p, float* __restrict__ m,
                                                       float* __restrict__ v,
@@ -857,9 +854,9 @@ Bn0AdamDev bn0adam_dev(const Bn0Adam& a) {
   const dcue_model* md = a.md;
   Bn0AdamDev d;
   d.p = md->params; d.m = md->exp_avg; d.v = md->exp_avg_sq; d.g = md->grads;
-  d.o_w1 = a.poff[2]; d.o_cb1 = a.poff[3];
-  d.o_g0 = a.bn ? a.poff[0] : -1; d.o_b0 = a.bn ? a.poff[1] : -1;
-  d.o_g1 = a.bn ? a.poff[4] : -1; d.o_b1 = a.bn ? a.poff[5] : -1;
+  d.o_w1 = a.poff[seg_conv_w(1)]; d.o_cb1 = a.poff[seg_conv_b(1)];
+  d.o_g0 = a.bn ? a.poff[seg_bn_w(0)] : -1; d.o_b0 = a.bn ? a.poff[seg_bn_b(0)] : -1;
+  d.o_g1 = a.bn ? a.poff[seg_bn_w(1)] : -1; d.o_b1 = a.bn ? a.poff[seg_bn_b(1)] : -1;
   d.sc = form_scalars(&a.args);
   d.seg1 = pack_args(md, a.poff).seg[0];
   d.wpack = md->wpack;
@@ -938,7 +935,7 @@ PackArgs pack_args(const dcue_model* md, const int64_t* poff) {
     sg.cin = l == 1 ? kMels : H;
     sg.cout = l == 5 ? d : H;
     sg.ks = layer_geom(l).ks;
-    sg.src = poff[2 + 4 * (l - 1)];  // conv.layer{l}.weight
+    sg.src = poff[seg_conv_w(l)];
     sg.fwd = wl.conv_fwd[l];
     sg.bwd = l >= 2 ? wl.conv_bwd[l] : -1;
     sg.f16 = wl.conv_f16[l];
@@ -950,7 +947,7 @@ PackArgs pack_args(const dcue_model* md, const int64_t* poff) {
   tx.cinp = st_word(&md->dims);
   tx.cout = st_text(&md->dims);
   tx.ks = 3;
-  tx.src = poff[28];
+  tx.src = poff[SEG_TX_W];
   tx.fwd = tx.bwd = tx.f16b = -1;
   tx.f16 = wl.text_f16;
   if (!tower_text(&md->dims)) tx.cout = tx.cin = 0;  // empty: no element lies in it

@@ -400,17 +400,10 @@ struct Ctx {
   float* dgamma(const Ws& w, int l) const;
   float* dbeta(const Ws& w, int l) const;
 };
-// segment indices
-int seg_bn_w(int l) { return l == 0 ? 0 : 4 + 4 * (l - 1); }
-int seg_bn_b(int l) { return l == 0 ? 1 : 5 + 4 * (l - 1); }
 const float* Ctx::gamma(const Ws& w, int l) const { return bn ? P(seg_bn_w(l)) : w.ones; }
 const float* Ctx::beta(const Ws& w, int l) const { return bn ? P(seg_bn_b(l)) : w.zeros; }
 float* Ctx::dgamma(const Ws& w, int l) const { return bn ? Gd(seg_bn_w(l)) : w.sink; }
 float* Ctx::dbeta(const Ws& w, int l) const { return bn ? Gd(seg_bn_b(l)) : w.sink + w.cmax; }
-int seg_conv_w(int l) { return 2 + 4 * (l - 1); }
-int seg_conv_b(int l) { return 3 + 4 * (l - 1); }
-constexpr int SEG_FC_W = 22, SEG_FC_B = 23, SEG_L1_W = 24, SEG_L1_B = 25, SEG_L2_W = 26, SEG_L2_B = 27;
-constexpr int SEG_TX_W = 28, SEG_TX_B = 29;
 
 int init_ctx(Ctx* c, const dcue_model* m) {
   int st = check_dims(&m->dims);

@@ -221,6 +221,22 @@ __device__ __forceinline__ float bn0_elem(const float* __restrict__ G, const flo
   db = fmaf(w, sv, db);
   return fmaf(ch.ga, gv, ch.be * sv);
 }
+// ------------------------------------------------------------------ dense parameter segments
+// Indices into dcue_param_layout's offsets, in the order capi.hip's param_sizes lays them out: bn0,
+// then per conv layer l = 1..5 its weight, bias and bn_l, the fc, the user tower's two linears, the
+// text convolution.
+constexpr int seg_bn_w(int l) { return l == 0 ? 0 : 4 + 4 * (l - 1); }
+constexpr int seg_bn_b(int l) { return l == 0 ? 1 : 5 + 4 * (l - 1); }
+constexpr int seg_conv_w(int l) { return 2 + 4 * (l - 1); }
+constexpr int seg_conv_b(int l) { return 3 + 4 * (l - 1); }
+constexpr int SEG_FC_W = 22, SEG_FC_B = 23, SEG_L1_W = 24, SEG_L1_B = 25, SEG_L2_W = 26, SEG_L2_B = 27;
+constexpr int SEG_TX_W = 28, SEG_TX_B = 29;
+static_assert(SEG_FC_W == seg_bn_b(5) + 1 && SEG_TX_B + 1 == DCUE_N_DENSE_SEGMENTS, "one index per segment");
+static_assert(DCUE_SEG_LATE == seg_conv_w(2), "the late segments are bn0, conv 1 and bn1");
+// host scalars of one Adam step as torch.optim.Adam forms them (adam.hip; AdamScalars: adam_replay.h)
+struct AdamScalars;
+AdamScalars form_scalars(const dcue_adam_args* a);
+
 // split plans (StepOpts::dense_split): bn0's gradients and, in the same launch, Adam over segments
 // [0, DCUE_SEG_LATE) -- bn0, conv 1 (with its weight repack), bn1 -- every one of which this
 // kernel's workgroups complete (workgroup c owns input channel c; workgroups 0 / 1 conv 1's bias and

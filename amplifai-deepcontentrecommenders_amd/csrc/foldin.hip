@@ -31,15 +31,12 @@
 
 namespace dcue {
 
-AdamScalars form_scalars(const dcue_adam_args* a);  // adam.hip
-
 constexpr int kFiThreads = 1024;
 constexpr int kFiWaves = kFiThreads / 64;
 constexpr int kFiTile = 16;              // users per workgroup
 constexpr int kFiHist = 256;             // history entries per user held in LDS (longer ones: global)
 constexpr int kFiLdsBudget = 156 * 1024; // one workgroup per CU; 4 KB left for the static arrays
 constexpr int kFiMaxSteps = 4096, kFiMaxNeg = 256, kFiMaxPos = 1024;
-constexpr int kFiSegW1 = 24, kFiSegB1 = 25, kFiSegW2 = 26, kFiSegB2 = 27;  // dcue_param_layout
 
 __host__ __device__ constexpr int fi_pad16(int v) { return (v + 15) & ~15; }
 __host__ __device__ constexpr int fi_pitch(int v) { return fi_pad16(v) + 4; }
@@ -485,8 +482,8 @@ int dcue_user_foldin(const dcue_model* m, const float* cand_feat, int64_t n_cand
   const int dp = rank_dp(d);
   TRY(launch_rank_normalize(cand_feat, nullptr, n_cand, d, dp, w.cn, s));
   FoldArgs a;
-  a.W1 = m->params + poff[kFiSegW1]; a.b1 = m->params + poff[kFiSegB1];
-  a.W2 = m->params + poff[kFiSegW2]; a.b2 = m->params + poff[kFiSegB2];
+  a.W1 = m->params + poff[SEG_L1_W]; a.b1 = m->params + poff[SEG_L1_B];
+  a.W2 = m->params + poff[SEG_L2_W]; a.b2 = m->params + poff[SEG_L2_B];
   a.E = E; a.D = D; a.d = d; a.dp = dp;
   a.cn = w.cn; a.n_cand = n_cand; a.mask = cand_mask;
   a.hist_ptr = hist_ptr; a.hist_idx = hist_idx;

@@ -20,6 +20,7 @@
 // Scores of the positives are read back from the same S the histograms stream, so a positive meets
 // its own threshold as an exact tie (no recomputation can differ by an ulp).
 #include "dcue_internal.h"
+#include "rank_sort.h"
 
 namespace dcue {
 
@@ -52,6 +53,7 @@ int launch_rank_normalize(const float* x, const int32_t* rows, int64_t n, int d,
 // S[q][c] for q < nq, c < nc. Wave w owns candidate columns 16w..16w+15 of the tile and all four
 // 16-query row tiles; k is split across the four lane groups (g = lane>>4 covers k = g*DP/4 + j), so
 // every lane reads DP/4 consecutive floats of its row.
+// k_topk_scores (topk.hip) restates the MFMA loop below and promises its bits: edit both together.
 __global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ qn, int nq,
                                                      const float* __restrict__ cn, int64_t nc, int dp,
                                                      float* __restrict__ S, int64_t ldS) {
@@ -100,14 +102,6 @@ __global__ __launch_bounds__(256) void k_rank_scores(const float* __restrict__ q
   }
 }
 
-__device__ __forceinline__ uint32_t float_order(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float order_float(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
 struct RankWs {
   float* thr;        // [QB][cap] ascending thresholds
   uint8_t* thr_cls;  // [QB][cap] list bits of each threshold's positive
@@ -138,7 +132,7 @@ __global__ __launch_bounds__(256) void k_rank_thresholds(const float* __restrict
       const float sc = S[(int64_t)i * ldS + c];
       if (!isfinite(sc)) bad = 1;
       const int slot = atomicAdd(&cnt, 1);
-      if (slot < kRankCap) key[slot] = ((uint64_t)float_order(sc) << 8) | k;
+      if (slot < kRankCap) key[slot] = ((uint64_t)ord_key(sc) << 8) | k;
     }
   }
   __syncthreads();
@@ -157,24 +151,9 @@ __global__ __launch_bounds__(256) void k_rank_thresholds(const float* __restrict
   while (np2 < n) np2 <<= 1;
   for (int k = n + tid; k < np2; k += 256) key[k] = ~0ull;
   __syncthreads();
-  // bitonic sort, ascending
-  for (int size = 2; size <= np2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < np2 / 2; t += 256) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool up = (lo & size) == 0;
-        const uint64_t a = key[lo], c = key[hi];
-        if ((a > c) == up) {
-          key[lo] = c;
-          key[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  block_bitonic_sort<false>(key, np2);  // ascending
   for (int k = tid; k < n; k += 256) {
-    w.thr[(int64_t)i * kRankCap + k] = order_float((uint32_t)(key[k] >> 8));
+    w.thr[(int64_t)i * kRankCap + k] = ord_value((uint32_t)(key[k] >> 8));
     w.thr_cls[(int64_t)i * kRankCap + k] = (uint8_t)(key[k] & 0xff);
   }
   if (tid == 0) w.n_thr[i] = n;
@@ -430,14 +409,10 @@ int dcue_rank_metrics(const float* query_feat, int64_t n_query_rows, const float
     attr = true;
   }
   DCUE_HIP_CHECK(hipMemsetAsync(w.status, 0xff, sizeof(int32_t), s));
-  DCUE_LAUNCH(k_rank_normalize, dim3((unsigned)((n_cand + 3) / 4)), dim3(256), 0, s, cand_feat,
-              (const int32_t*)nullptr, n_cand, d, dp, cn);
-  DCUE_LAUNCH_CHECK();
+  TRY(launch_rank_normalize(cand_feat, nullptr, n_cand, d, dp, cn, s));
   for (int32_t q0 = 0; q0 < n_queries; q0 += query_batch) {
     const int nq = n_queries - q0 < query_batch ? n_queries - q0 : query_batch;
-    DCUE_LAUNCH(k_rank_normalize, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, query_feat,
-                queries + q0, (int64_t)nq, d, dp, qn);
-    DCUE_LAUNCH_CHECK();
+    TRY(launch_rank_normalize(query_feat, queries + q0, nq, d, dp, qn, s));
     DCUE_LAUNCH(k_rank_scores, dim3((unsigned)((n_cand + kRankTile - 1) / kRankTile), (unsigned)((nq + kRankTile - 1) / kRankTile)),
                 dim3(256), lds_scores, s, qn, nq, cn, n_cand, dp, S, n_cand);
     DCUE_LAUNCH_CHECK();

@@ -27,6 +27,7 @@
 // order, so the result does not depend on tiling, splits or the arrival order of LDS atomics. Key 0
 // (below the key of -inf) marks an empty slot. NaN scores are never keyed.
 #include "dcue_internal.h"
+#include "rank_sort.h"
 
 namespace dcue {
 
@@ -107,20 +108,12 @@ __device__ void topk_compact(const TopkLds& L, int k, int lkp, int n_valid, cons
 #pragma unroll
   for (int i = 0; i < NE; ++i) L.app[tid + 256 * i] = key[i];
   __syncthreads();
-  // bitonic sort of each 32-slot buffer, descending
+  // bitonic sort of each 32-slot buffer, descending: the QT buffers side by side in one pass per
+  // stage (block_bitonic_sort would take QT passes, each with its own barriers)
   for (int size = 2; size <= kTopkApp; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < QT * (kTopkApp / 2); t += 256) {
-        const int ql = t / (kTopkApp / 2), tt = t % (kTopkApp / 2);
-        const int lo = 2 * tt - (tt & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        unsigned long long* b = L.app + ql * kTopkApp;
-        const unsigned long long x = b[lo], y = b[hi];
-        if ((x < y) == desc) {
-          b[lo] = y;
-          b[hi] = x;
-        }
-      }
+      for (int t = tid; t < QT * (kTopkApp / 2); t += 256)
+        bitonic_cx<true>(L.app + t / (kTopkApp / 2) * kTopkApp, t % (kTopkApp / 2), size, stride);
       __syncthreads();
     }
   }
@@ -134,6 +127,8 @@ __device__ void topk_compact(const TopkLds& L, int k, int lkp, int n_valid, cons
     if (y > *t) *t = y;
   }
   __syncthreads();
+  // (written out, not bitonic_cx: through the helper this kernel compiles to another instruction
+  // order, and its speed moved with it)
   for (int stride = kp >> 1; stride > 0; stride >>= 1) {
     for (int t = tid; t < (QT << lkp) / 2; t += 256) {
       const int ql = t >> (lkp - 1), tt = t & ((kp >> 1) - 1);
@@ -172,6 +167,9 @@ __device__ __forceinline__ bool topk_eligible(const TopkArgs& a, const TopkLds& 
 
 // MT 16-query row tiles per workgroup (QT = 16 MT queries); wave w owns candidate columns 16w..16w+15
 // of each 64-candidate tile
+// The MFMA loop restates k_rank_scores' (rank.hip) and must stay in step with it: recommend-versus-score
+// parity rests on the two loops' k order. A shared forceinline loop was tried; it changed how the
+// compiler keeps the accumulators in both kernels, and top-K ran 1 % to 5 % slower by the variant.
 template <int MT>
 __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
   constexpr int QT = 16 * MT;
@@ -342,27 +340,14 @@ __global__ __launch_bounds__(256) void k_topk_merge(const unsigned long long* __
                                                     const int32_t* __restrict__ pflags, int S, int k, int q_offset,
                                                     int32_t* __restrict__ out_idx, float* __restrict__ out_score,
                                                     int32_t* __restrict__ out_count, int32_t* __restrict__ out_flags) {
-  __shared__ unsigned long long key[kTopkMaxSplit * DCUE_TOPK_MAX_K];
+  __shared__ uint64_t key[kTopkMaxSplit * DCUE_TOPK_MAX_K];
   const int i = blockIdx.x, tid = threadIdx.x;
   const int n = S * k;
   int np2 = 1;
   while (np2 < n) np2 <<= 1;
   for (int e = tid; e < np2; e += 256) key[e] = e < n ? parts[(size_t)i * n + e] : 0ull;
   __syncthreads();
-  for (int size = 2; size <= np2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < np2 / 2; t += 256) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long x = key[lo], y = key[hi];
-        if ((x < y) == desc) {
-          key[lo] = y;
-          key[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  block_bitonic_sort<true>(key, np2);  // descending
   const size_t o = (size_t)(q_offset + i) * k;
   for (int j = tid; j < k; j += 256) {
     const unsigned long long v = key[j];

@@ -543,11 +543,7 @@ class DCUE(Trainer):
         """rank.TopK per (kind, dataset, exclude_seen), cached as _evaluator caches its lists."""
         key = ("topk", kind, id(ds), bool(exclude_seen))
         if key not in self._evals:
-            mask = (self._item_meta >= 0).astype(np.uint8)  # items without audio have zero factors
-            if ds is not None:
-                split = np.zeros_like(mask)
-                split[ds.split_items()] = 1
-                mask &= split
+            mask = self._cand_mask(ds)
             if kind == "song":
                 ptr, idx = rank.identity_csr(len(mask))
             elif exclude_seen:

@@ -12,6 +12,8 @@ and a per-query exclusion CSR, fused so that the score matrix is never written.
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -66,29 +68,64 @@ def mean_until_missing(values, has_pos):
     return float(np.mean(np.asarray(values, np.float64)[:stop]))
 
 
-class RankEvaluator:
+def _upload_csr(ptr, idx, device):
+    """(int64 pointers, int32 indices) on the device; an empty index array becomes one unused entry,
+    so that its address is never null."""
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    return (torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(device),
+            torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(device))
+
+
+def _upload_mask(cand_mask, n_cand, device):
+    """(uint8 mask on the device, its length), or (None, n_cand) without a mask."""
+    if cand_mask is not None:
+        mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(device)
+        return mask, int(mask.numel())
+    if n_cand is None:
+        raise ValueError("n_cand is needed without a candidate mask")
+    return None, int(n_cand)
+
+
+def _check_shapes(cand_feat, n_cand, d, query_feat=None, ptr=None):
+    """The candidate factors are [n_cand, d]; the query factors have one row per CSR row."""
+    if cand_feat.shape[0] != n_cand or cand_feat.shape[1] != d:
+        raise ValueError("candidate factors %s do not match %d candidates / d=%d" % (tuple(cand_feat.shape), n_cand, d))
+    if ptr is not None and query_feat.shape[0] + 1 != ptr.numel():
+        raise ValueError("query factors have %d rows, the CSR %d" % (query_feat.shape[0], ptr.numel() - 1))
+
+
+def _nonfinite_error(queries, bad):
+    """sklearn's wording for the first query of `bad` (a cosine of finite factors is finite:
+    non-finite factors make NaN scores)."""
+    return ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
+                      "finite)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+
+
+class _Workspace:
+    """The grow-only device workspace of one entry point, sized by its dcue_*_workspace_bytes."""
+
+    _ws = None
+
+    def _nbytes(self, name, *args):
+        nbytes = ctypes.c_size_t()
+        nat.check(getattr(nat.lib(), name)(*args, ctypes.byref(nbytes)), name)
+        return nbytes.value
+
+    def _grow(self, nbytes):
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+
+class RankEvaluator(_Workspace):
     """Device-resident candidate lists for one (query kind, pred split, truth split) and the
     workspace of dcue_rank_metrics."""
 
     def __init__(self, inputs, device, max_score_bytes=1 << 30):
         self.device = torch.device(device)
-        self.pos_ptr = torch.from_numpy(inputs["pos_ptr"]).to(self.device)
-        self.pos_idx = torch.from_numpy(inputs["pos_idx"]).to(self.device)
-        if self.pos_idx.numel() == 0:
-            self.pos_idx = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.cand_class = torch.from_numpy(inputs["cand_class"]).to(self.device)
-        self.n_cand = int(self.cand_class.numel())
+        self.pos_ptr, self.pos_idx = _upload_csr(inputs["pos_ptr"], inputs["pos_idx"], self.device)
+        self.cand_class, self.n_cand = _upload_mask(inputs["cand_class"], None, self.device)
         self.max_score_bytes = max_score_bytes
-        self._ws = None
-
-    def _workspace(self, d, qb):
-        import ctypes
-        nbytes = ctypes.c_size_t()
-        nat.check(nat.lib().dcue_rank_workspace_bytes(self.n_cand, d, qb, ctypes.byref(nbytes)),
-                  "dcue_rank_workspace_bytes")
-        if self._ws is None or self._ws.numel() < nbytes.value:
-            self._ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
-        return self._ws
 
     def metrics(self, query_feat, cand_feat, queries, mode):
         """(auc, ap, has_pos) numpy arrays, one entry per query (fp64).
@@ -101,12 +138,7 @@ class RankEvaluator:
         nat.require_gpu(cand_feat, "cand_feat")
         query_feat = query_feat.contiguous().float()
         cand_feat = cand_feat.contiguous().float()
-        if cand_feat.shape[0] != self.n_cand or cand_feat.shape[1] != query_feat.shape[1]:
-            raise ValueError("candidate factors %s do not match %d candidates / d=%d"
-                             % (tuple(cand_feat.shape), self.n_cand, query_feat.shape[1]))
-        if query_feat.shape[0] + 1 != self.pos_ptr.numel():
-            raise ValueError("query factors have %d rows, the CSR %d" % (query_feat.shape[0],
-                                                                          self.pos_ptr.numel() - 1))
+        _check_shapes(cand_feat, self.n_cand, query_feat.shape[1], query_feat, self.pos_ptr)
         q = torch.as_tensor(np.asarray(queries, dtype=np.int32)).to(self.device)
         nq = int(q.numel())
         auc = torch.zeros(max(nq, 1), dtype=torch.float64, device=self.device)
@@ -117,7 +149,7 @@ class RankEvaluator:
                 raise IndexError("query index out of range")
             d = int(query_feat.shape[1])
             qb = int(max(16, min(nq, self.max_score_bytes // (4 * max(self.n_cand, 1)))))
-            ws = self._workspace(d, qb)
+            ws = self._grow(self._nbytes("dcue_rank_workspace_bytes", self.n_cand, d, qb))
             nat.check(nat.lib().dcue_rank_metrics(
                 nat.ptr(query_feat), query_feat.shape[0], nat.ptr(cand_feat), self.n_cand, d, nat.ptr(q), nq,
                 nat.ptr(self.pos_ptr), nat.ptr(self.pos_idx), nat.ptr(self.cand_class), int(mode), qb,
@@ -128,9 +160,7 @@ class RankEvaluator:
         nonfinite = (flag & 2).astype(bool)
         checked = nonfinite[:int(np.argmin(ok))] if (mode == nat.RANK_SPLIT and not ok.all()) else nonfinite
         if checked.any():
-            # (a cosine of finite factors is finite: non-finite factors make NaN scores)
-            raise ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
-                             "finite)" % int(np.asarray(queries)[int(np.argmax(checked))]))
+            raise _nonfinite_error(queries, checked)
         sane = ~nonfinite
         if not (np.all((auc[sane] >= 0.0) & (auc[sane] <= 1.0)) and np.all((ap[sane] >= 0.0) & (ap[sane] <= 1.0))):
             raise RuntimeError("dcue_rank_metrics: AUC / AP outside [0, 1]")
@@ -142,7 +172,7 @@ def identity_csr(n):
     return np.arange(n + 1, dtype=np.int64), np.arange(n, dtype=np.int32)
 
 
-class TopK:
+class TopK(_Workspace):
     """Device-resident exclusion lists and candidate mask of one recommendation setting and the
     grow-only workspace of dcue_topk -- RankEvaluator's counterpart for "the k best candidates".
 
@@ -158,30 +188,11 @@ class TopK:
             raise ValueError("excl_ptr and excl_idx go together")
         self.excl_ptr = self.excl_idx = None
         if excl_ptr is not None:
-            self.excl_ptr = torch.from_numpy(np.ascontiguousarray(excl_ptr, dtype=np.int64)).to(self.device)
-            idx = np.ascontiguousarray(excl_idx, dtype=np.int32)
-            self.excl_idx = torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(self.device)
-        self.cand_mask = None
-        if cand_mask is not None:
-            self.cand_mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(self.device)
-            n_cand = int(self.cand_mask.numel())
-        if n_cand is None:
-            raise ValueError("n_cand is needed without a candidate mask")
-        self.n_cand = int(n_cand)
-        self._ws = None
+            self.excl_ptr, self.excl_idx = _upload_csr(excl_ptr, excl_idx, self.device)
+        self.cand_mask, self.n_cand = _upload_mask(cand_mask, n_cand, self.device)
 
     def workspace_bytes(self, d, qb, k, cand_split=0):
-        import ctypes
-        nbytes = ctypes.c_size_t()
-        nat.check(nat.lib().dcue_topk_workspace_bytes(self.n_cand, d, qb, k, cand_split, ctypes.byref(nbytes)),
-                  "dcue_topk_workspace_bytes")
-        return nbytes.value
-
-    def _workspace(self, d, qb, k, cand_split):
-        nbytes = self.workspace_bytes(d, qb, k, cand_split)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._nbytes("dcue_topk_workspace_bytes", self.n_cand, d, qb, k, cand_split)
 
     def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
         """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
@@ -190,12 +201,7 @@ class TopK:
         nat.require_gpu(cand_feat, "cand_feat")
         query_feat = query_feat.contiguous().float()
         cand_feat = cand_feat.contiguous().float()
-        if cand_feat.shape[0] != self.n_cand or cand_feat.shape[1] != query_feat.shape[1]:
-            raise ValueError("candidate factors %s do not match %d candidates / d=%d"
-                             % (tuple(cand_feat.shape), self.n_cand, query_feat.shape[1]))
-        if self.excl_ptr is not None and query_feat.shape[0] + 1 != self.excl_ptr.numel():
-            raise ValueError("query factors have %d rows, the CSR %d" % (query_feat.shape[0],
-                                                                          self.excl_ptr.numel() - 1))
+        _check_shapes(cand_feat, self.n_cand, query_feat.shape[1], query_feat, self.excl_ptr)
         k = int(k)
         if not 1 <= k <= nat.TOPK_MAX_K:
             raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, k))
@@ -210,7 +216,7 @@ class TopK:
                 raise IndexError("query index out of range")
             d = int(query_feat.shape[1])
             qb = int(min(nq, self.DEFAULT_QUERY_BATCH if query_batch is None else query_batch))
-            ws = self._workspace(d, qb, k, int(cand_split))
+            ws = self._grow(self.workspace_bytes(d, qb, k, int(cand_split)))
             nat.check(nat.lib().dcue_topk(
                 nat.ptr(query_feat), query_feat.shape[0], nat.ptr(cand_feat), self.n_cand, d, nat.ptr(q), nq,
                 nat.ptr(self.excl_ptr), nat.ptr(self.excl_idx), nat.ptr(self.cand_mask), k, qb, int(cand_split),
@@ -228,8 +234,7 @@ class TopK:
         flags = flags.cpu().numpy()
         bad = (flags & 2).astype(bool)
         if bad.any():
-            raise ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
-                             "finite)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+            raise _nonfinite_error(queries, bad)
         return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
 
 
@@ -244,7 +249,7 @@ def histories_csr(rows):
     return ptr, (np.concatenate(idx) if idx else np.zeros(0, np.int32)).astype(np.int32)
 
 
-class FoldIn:
+class FoldIn(_Workspace):
     """Device-resident candidate mask and the grow-only workspace of dcue_user_foldin -- TopK's
     counterpart for users outside the trained table: one fresh embedding row per user, learned
     against the frozen towers in one kernel launch for all steps (include/dcue.h).
@@ -256,34 +261,16 @@ class FoldIn:
 
     def __init__(self, cand_mask, device, n_cand=None):
         self.device = torch.device(device)
-        self.cand_mask = None
-        if cand_mask is not None:
-            self.cand_mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(self.device)
-            n_cand = int(self.cand_mask.numel())
-        if n_cand is None:
-            raise ValueError("n_cand is needed without a candidate mask")
-        self.n_cand = int(n_cand)
-        self._ws = None
+        self.cand_mask, self.n_cand = _upload_mask(cand_mask, n_cand, self.device)
 
     def workspace_bytes(self, dims, n_users, max_pos, n_neg):
-        import ctypes
-        nbytes = ctypes.c_size_t()
-        nat.check(nat.lib().dcue_foldin_workspace_bytes(ctypes.byref(dims), self.n_cand, n_users, max_pos, n_neg,
-                                                        ctypes.byref(nbytes)), "dcue_foldin_workspace_bytes")
-        return nbytes.value
-
-    def _workspace(self, dims, n_users, max_pos, n_neg):
-        nbytes = self.workspace_bytes(dims, n_users, max_pos, n_neg)
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._nbytes("dcue_foldin_workspace_bytes", ctypes.byref(dims), self.n_cand, n_users, max_pos, n_neg)
 
     def _csr(self, hist_ptr, hist_idx):
-        ptr = torch.from_numpy(np.ascontiguousarray(hist_ptr, dtype=np.int64)).to(self.device)
         idx = np.ascontiguousarray(hist_idx, dtype=np.int32)
         if len(idx) and (idx.min() < 0 or idx.max() >= self.n_cand):
             raise IndexError("history index out of range")
-        return ptr, torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(self.device)
+        return _upload_csr(hist_ptr, idx, self.device)
 
     @staticmethod
     def config(steps, n_neg, max_pos, margin, lr, beta1, beta2, eps, weight_decay=0.0, seed=0):
@@ -303,14 +290,11 @@ class FoldIn:
         init [n, E]: the rows' starting values (not modified); hist_ptr / hist_idx: the histories of
         rows row0 .. row0 + n - 1 at those positions of the CSR. Users are passed user_batch at a time
         with their global row, so the result does not depend on user_batch."""
-        import ctypes
         nat.require_gpu(cand_feat, "cand_feat")
         nat.require_gpu(init, "init")
         cand_feat = cand_feat.contiguous().float()
         d, E = int(model.dims.feature_dim), int(model.dims.user_embdim)
-        if cand_feat.shape[0] != self.n_cand or cand_feat.shape[1] != d:
-            raise ValueError("candidate factors %s do not match %d candidates / d=%d"
-                             % (tuple(cand_feat.shape), self.n_cand, d))
+        _check_shapes(cand_feat, self.n_cand, d)
         n = int(init.shape[0])
         if init.dim() != 2 or init.shape[1] != E:
             raise ValueError("init must be [n, %d], got %s" % (E, tuple(init.shape)))
@@ -326,7 +310,7 @@ class FoldIn:
         ub = int(min(max(n, 1), self.DEFAULT_USER_BATCH if user_batch is None else user_batch))
         if ub < 1:
             raise ValueError("user_batch must be positive")
-        ws = self._workspace(model.dims, ub, int(cfg.max_pos), int(cfg.n_neg))
+        ws = self._grow(self.workspace_bytes(model.dims, ub, int(cfg.max_pos), int(cfg.n_neg)))
         for u0 in range(0, n, ub):
             nu = min(ub, n - u0)
             nat.check(nat.lib().dcue_user_foldin(
@@ -341,7 +325,6 @@ class FoldIn:
     def negatives(self, hist_ptr, hist_idx, n, cfg, step, row0=0):
         """int32 [n, max_pos, n_neg] device tensor: the negatives dcue_user_foldin draws at `step` for
         rows row0 .. row0 + n - 1 (-1: a dropped slot, or a positive slot the history does not fill)."""
-        import ctypes
         ptr, idx = self._csr(hist_ptr, hist_idx)
         out = torch.full((max(n, 1), int(cfg.max_pos), int(cfg.n_neg)), -1, dtype=torch.int32, device=self.device)
         nat.check(nat.lib().dcue_foldin_negatives(self.n_cand, nat.ptr(self.cand_mask), nat.ptr(ptr), nat.ptr(idx),

@@ -13,10 +13,9 @@ import torch
 
 import foldin_reference as R
 from conftest import ROOT
+from kernel_resources import HIPCC, kernel_resources
 
-PKG = os.path.join(ROOT, "amplifai-deepcontentrecommenders_amd")
 HEADER = os.path.join(ROOT, "include", "dcue.h")
-HIPCC = "/opt/rocm/bin/hipcc"
 OK, INVALID, UNSUPPORTED, WORKSPACE = 0, 1, 2, 4
 NEW = ("dcue_foldin_workspace_bytes", "dcue_user_foldin", "dcue_foldin_negatives")
 
@@ -261,21 +260,7 @@ def test_thirty_step_cases_meet_the_condition(case):
 # ------------------------------------------------------------------------------- compiled kernels
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_foldin_kernels_use_no_scratch(tmp_path):
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-c",
-                          os.path.join(PKG, "csrc", "foldin.hip"), "-o", str(tmp_path / "foldin.o"),
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).split(" ")[0]] = int(m.group(2))
+    res = kernel_resources("foldin.hip", tmp_path, ["-ffp-contract=off"])
     found = {k: v for k, v in res.items() if "k_foldin" in k}
     assert len([k for k in found if "k_foldin_negatives" in k]) == 1
     assert len([k for k in found if "k_foldinILi" in k]) == 3, sorted(found)  # the three residency tiers

@@ -5,16 +5,14 @@ kernels' scratch use."""
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import topk_reference as T
 from conftest import ROOT
+from kernel_resources import HIPCC, kernel_resources
 
-PKG = os.path.join(ROOT, "amplifai-deepcontentrecommenders_amd")
-HIPCC = "/opt/rocm/bin/hipcc"
 OK, INVALID, UNSUPPORTED, WORKSPACE = 0, 1, 2, 4
 
 
@@ -172,21 +170,7 @@ def test_topk_unsupported_and_workspace():
 # ------------------------------------------------------------------------------- compiled kernels
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_topk_kernels_use_no_scratch(tmp_path):
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), "-c",
-                          os.path.join(PKG, "csrc", "topk.hip"), "-o", str(tmp_path / "topk.o"),
-                          "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    res, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            res[cur] = {}
-            continue
-        m = re.search(r"(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and cur:
-            res[cur][m.group(1).split(" ")[0]] = int(m.group(2))
+    res = kernel_resources("topk.hip", tmp_path)
     for kern in ("k_topk_scores", "k_topk_merge"):
         found = {k: v for k, v in res.items() if kern in k}
         assert found, "no %s instance found" % kern
