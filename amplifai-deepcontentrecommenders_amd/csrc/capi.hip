@@ -329,7 +329,7 @@ size_t carve(const dcue_dims* d, int B, int N, int M, void* base, Ws* w) {
   long wp = 0, bp = 0;
   for (int l = 1; l <= 5; ++l) {
     const int cin = l == 1 ? kMels : H, cout = l == 5 ? D : H;
-    const long nch = wgrad_nchunk(l, M, cout, cin);
+    const long nch = wgrad_nchunk(l, M, cout, cin, true);  // (so the size never falls as M grows)
     const long e = nch * cout * cin * layer_geom(l).ks;
     if (e > wp) wp = e;
     if (nch * 5 * cout > bp) bp = nch * 5 * cout;
@@ -340,7 +340,7 @@ size_t carve(const dcue_dims* d, int B, int N, int M, void* base, Ws* w) {
   }
   for (int l = 2; l <= 6; ++l) {  // 6: the fc layer (a 1x1 conv over bn5(y5), D -> D)
     const int cin = l == 6 ? D : H, cout = l >= 5 ? D : H;
-    const long nch = wgrad_nchunk(l, M, cout, cin);
+    const long nch = wgrad_nchunk(l, M, cout, cin, true);  // (so the size never falls as M grows)
     w->wpm[l - 2] = ar.take<float>(nch * cout * cin * layer_geom(l == 6 ? 5 : l).ks);
     w->bpm[l - 2] = ar.take<float>(nch * cout);
   }
@@ -722,6 +722,30 @@ int dcue_workspace_bytes(const dcue_dims* dims, int32_t max_rows, int32_t max_ne
   if (!bytes || max_rows <= 0 || max_neg < 0 || max_items <= 0) return DCUE_ERR_INVALID;
   Ws w;
   *bytes = carve(dims, max_rows, max_neg, max_items, nullptr, &w);
+  return DCUE_OK;
+}
+
+int dcue_debug_launch_shape(const dcue_dims* dims, int32_t layout, int32_t B, int32_t N, int32_t M,
+                            int32_t* out_host, int32_t cap) {
+  TRY(check_dims(dims));
+  if (!out_host || cap < DCUE_LAUNCH_SHAPE_WORDS || B <= 0 || N < 0 || M <= 0) return DCUE_ERR_INVALID;
+  const bool gather = layout == DCUE_LAYOUT_GATHER;
+  if (layout == DCUE_LAYOUT_CATALOGUE ? (long)M != (long)B * (1 + N) : (!gather || M < B)) return DCUE_ERR_INVALID;
+  // the arguments backward_impl / forward_impl give the launchers
+  const int H = st_hidden(dims), D = st_feature(dims);
+  const bool fc = !tower_res(dims) && !tower_text(dims);  // the fc rides in the item gradient / layer 3-5 launch
+  int32_t* o = out_host;
+  for (int l = 1; l <= 5; ++l, o += 5) conv_fwd_shape(l, l == 1 ? kMels : H, l == 5 ? D : H, M, o);
+  for (int l = 2; l <= 5; ++l, o += 5) conv_dgrad_shape(l, l == 5 ? D : H, H, M, o);
+  for (int l = 1; l <= 6; ++l, o += 4) {
+    if (l == 6 && !fc) {  // res / text towers: the fc weight gradient is a plain GEMM
+      o[0] = -1;
+      o[1] = o[2] = o[3] = 0;
+      continue;
+    }
+    wgrad_shape(l, M, l >= 5 ? D : H, l == 1 ? kMels : l == 6 ? D : H, SRC_TRACK_F16, l <= 2, o);
+  }
+  tail_shape(N, M, D, gather, gather && M <= kCopyListMaxItems, fc, o);
   return DCUE_OK;
 }
 

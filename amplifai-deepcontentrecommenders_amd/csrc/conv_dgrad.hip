@@ -20,13 +20,18 @@ static bool dgrad_f16_on() {
 
 constexpr long kDgradF16MinRows = 8192;  // output rows M * Lin of a launch
 
+// whether an input gradient of `rows` output rows (M * Lin) runs on split-f16 MFMA
+static bool dgrad_f16(bool have_operands, long rows) {
+  return have_operands && dgrad_f16_on() && rows >= kDgradF16MinRows;
+}
+
 template <int L, int KC, int TW>
 static int dgrad_layer_tw(const RowsArgs& a, hipStream_t s) {
   constexpr LayerGeom gm = layer_geom(L);
   static_assert(KC % 32 == 0, "split-f16 chunks are 32 channels");
   // (small launches stay on f32: in-batch, the split's range stage and fill cost the one-tile
   // workgroups 1-3 us each, rocprof; catalogue layer 2: 128 -> 54 us)
-  if (a.wpack16 && a.in_range && dgrad_f16_on() && (long)a.M * gm.lin >= kDgradF16MinRows)
+  if (dgrad_f16(a.wpack16 && a.in_range, (long)a.M * gm.lin))
     return run_rows<1, SRC_DZ, KC, gm.ks, gm.ks - 1 - gm.pad, gm.lp * gm.pool, gm.lin, 1, TW, gm.lp,
                     gm.pool, true>(a, s);
   return run_rows<1, SRC_DZ, KC, gm.ks, gm.ks - 1 - gm.pad, gm.lp * gm.pool, gm.lin, 1, TW, gm.lp,
@@ -54,6 +59,14 @@ static int dgrad_kc(int kc, const RowsArgs& a, hipStream_t s) {
     case 256: return dgrad_layer<L, 256>(a, s);
     default: return DCUE_ERR_UNSUPPORTED;
   }
+}
+
+// dcue_debug_launch_shape: what launch_conv_dgrad(layer, kc, ...) does for M items (a step always
+// passes the packed f16 operand and the gradient range)
+void conv_dgrad_shape(int layer, int kc, int nout, int M, int32_t* out) {
+  const LayerGeom gm = layer_geom(layer);
+  const long rows = (long)M * gm.lin;
+  rows_shape(M, gm.lin, choose_tw(rows, max_tw(gm.lin, gm.ks, kc)), nout, dgrad_f16(true, rows), out);
 }
 
 int launch_conv_dgrad(int layer, int kc, const RowsArgs& a, hipStream_t s) {

@@ -6,11 +6,14 @@ DCUE_KTRACE_READER(fwd)  // diagnostic builds only (dcue_common.h)
 
 namespace dcue {
 
+// whether a forward runs on split-f16 MFMA: its packed f16 operand is there and DCUE_CONV_F16 allows
+static bool fwd_f16(bool have_wpack16) { return have_wpack16 && conv_f16_on(); }
+
 template <int L, int KC, int SRC, int TW>
 static int fwd_layer_tw(const RowsArgs& a, hipStream_t s) {
   constexpr LayerGeom gm = layer_geom(L);
   static_assert(KC % 32 == 0, "split-f16 chunks are 32 channels");
-  if (a.wpack16 && conv_f16_on())
+  if (fwd_f16(a.wpack16 != nullptr))
     return run_rows<0, SRC, KC, gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, TW, 1, 1, true>(a, s);
   return run_rows<0, SRC, KC, gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, TW, 1, 1>(a, s);
 }
@@ -42,6 +45,14 @@ static int fwd_kc(int kc, int src, const RowsArgs& a, hipStream_t s) {
       default: return DCUE_ERR_UNSUPPORTED;
     }
   }
+}
+
+// dcue_debug_launch_shape: what launch_conv_fwd(layer, kc, ...) does for M items (steps and the
+// eval tower always pass the packed f16 operand)
+void conv_fwd_shape(int layer, int kc, int nout, int M, int32_t* out) {
+  const LayerGeom gm = layer_geom(layer);
+  const int R = gm.lp * gm.pool;
+  rows_shape(M, R, choose_tw((long)M * R, max_tw(R, gm.ks, kc)), nout, fwd_f16(true), out);
 }
 
 int launch_conv_fwd(int layer, int kc, int src, const RowsArgs& a, hipStream_t s) {

@@ -678,6 +678,9 @@ static int run_rows_pd(const RowsArgs& a, dim3 grid, size_t lds, hipStream_t s) 
   return DCUE_OK;
 }
 
+// The DEEP instantiation (weights requested a layer ahead): one-tile workgroups, at most one per CU
+static bool rows_deep(int tw, long wgs) { return tw == 1 && wgs <= 256; }
+
 template <int MODE, int SRC, int KC, int KS, int PADL, int LIN, int R, int POOL, int TW, int LPL,
           int POOLL, bool F16 = false>
 static int run_rows(const RowsArgs& a, hipStream_t s) {
@@ -688,7 +691,7 @@ static int run_rows(const RowsArgs& a, hipStream_t s) {
   static_assert(LDS + sizeof(ChanLds) <= 160 * 1024, "slab exceeds LDS");
   const long total = (long)a.M * R;
   dim3 grid((unsigned)((total + ROWS - 1) / ROWS), (unsigned)((a.nout + 127) / 128));
-  if (TW == 1 && (long)grid.x * grid.y <= 256)  // one-tile workgroups, one per CU: weights run ahead
+  if (rows_deep(TW, (long)grid.x * grid.y))  // one-tile workgroups, one per CU: weights run ahead
     return run_rows_pd<MODE, SRC, KC, KS, PADL, LIN, R, POOL, TW, LPL, POOLL, true, F16>(a, grid, LDS, s);
   return run_rows_pd<MODE, SRC, KC, KS, PADL, LIN, R, POOL, TW, LPL, POOLL, false, F16>(a, grid, LDS, s);
 }
@@ -752,6 +755,19 @@ constexpr int max_tw(int R, int KS, int KC) {
   return slab_bytes(R, KS, KC, 8) <= kSlabMax ? 8
        : slab_bytes(R, KS, KC, 4) <= kSlabMax ? 4
        : slab_bytes(R, KS, KC, 2) <= kSlabMax ? 2 : 1;
+}
+
+// dcue_debug_launch_shape's record of a k_conv_rows launch over M items of R rows at `tw` tiles per
+// workgroup (run_rows' grid): TW, DEEP, split-f16, the rows of the last workgroup (0: all 16 TW), and
+// whether some workgroup's rows belong to two items
+static void rows_shape(long M, int R, int tw, int nout, bool f16, int32_t* out) {
+  const long total = M * R, rows = 16L * tw;
+  const long wgs = ((total + rows - 1) / rows) * ((nout + 127) / 128);
+  out[0] = tw;
+  out[1] = rows_deep(tw, wgs) ? 1 : 0;
+  out[2] = f16 ? 1 : 0;
+  out[3] = (int32_t)(total % rows);
+  out[4] = (M > 1 && R % rows != 0) ? 1 : 0;
 }
 
 }  // namespace dcue

@@ -1466,6 +1466,24 @@ static bool w16t_layer(int layer, int cin) {
   return layer == 1 ? mode >= 1 : (layer == 2 && mode >= 2);
 }
 
+// split-K chunk length of the split-f16 kernels: whole stages (so whole pool windows), (wgrad_nchunk
+// picks counts that leave no chunk empty)
+static long w16_rows_per_chunk(long rows, int nchunk) {
+  const long rpc = (rows + nchunk - 1) / nchunk;
+  return (rpc + kW16Rows - 1) / kW16Rows * kW16Rows;
+}
+
+// split-K chunk length (WgradArgs::rows_per_chunk) of kernel `kernel` (WK_*) over `rows` conv rows:
+// every launcher's, and dcue_debug_launch_shape's
+static long wgrad_chunk_rows(int kernel, long rows, int nchunk) {
+  switch (kernel) {
+    case WK_CONV1: return 4L * ((rows / 4 + nchunk - 1) / nchunk);  // whole pool windows
+    case WK_F32:
+    case WK_MULTI_F32: return (rows + nchunk - 1) / nchunk;  // the last chunk may be short; rows past it are masked
+    default: return w16_rows_per_chunk(rows, nchunk);
+  }
+}
+
 // Layer-1 weight gradient (the step's largest MFMA kernel). The GEMM is
 // dW1[o][kc] = sum over conv-1 rows (item, t) of dz1[row][o] * xhat0[item][t + kx - 2][c], K = M*132
 // rows, kc = kx*128 + c. dz1 is BN1's backward through relu + max-pool: of each pool window's four
@@ -1700,8 +1718,7 @@ static int conv1_wgrad(const WgradArgs& a0, int nchunk, hipStream_t s) {
   }
   if (a0.cout % 16 != 0) return DCUE_ERR_UNSUPPORTED;  // argmax rows are loaded 16 channels at a time
   WgradArgs a = a0;
-  const long wins = (long)a.M * 33;
-  a.rows_per_chunk = (int)(4L * ((wins + nchunk - 1) / nchunk));  // whole pool windows
+  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_CONV1, (long)a.M * 132, nchunk);
   dim3 grid((unsigned)nchunk, (unsigned)(4 * kMels / kW1Tile), (unsigned)((a.cout + kW1Tile - 1) / kW1Tile));
   DCUE_LAUNCH(k_conv1_wgrad, grid, dim3(512), LDS, s, a);
   DCUE_LAUNCH_CHECK();
@@ -1809,13 +1826,6 @@ int launch_xhat0(int src, const void* tracks, const int32_t* item_track, int M, 
   return DCUE_OK;
 }
 
-// split-K chunk length of the split-f16 kernels: whole stages (so whole pool windows), (wgrad_nchunk
-// picks counts that leave no chunk empty)
-static long w16_rows_per_chunk(long rows, int nchunk) {
-  const long rpc = (rows + nchunk - 1) / nchunk;
-  return (rpc + kW16Rows - 1) / kW16Rows * kW16Rows;
-}
-
 // conv 1's split-f16 weight gradient on k_conv_wgrad1k (one tap per workgroup, round 6; needs
 // 128 input channels and cout <= 256) under DCUE_W1K=1. Off by default: at the in-batch shape it
 // measured 24.6-34.5 us (2-16 stages a chunk) against k_conv_wgrad16t's 19.9 us, although it writes
@@ -1828,7 +1838,10 @@ static bool w1k_layer1(int cin, int cout) {
   return on && wgrad_f16_on() && cin == kMels && cout % 4 == 0 && cout <= kW1kThreads;
 }
 
-int wgrad_nchunk(int layer, int M, int cout, int cin) {
+// bound: the count before the whole-stage rounding below -- never under the launch's count and, unlike
+// it, never smaller for a larger M (993 items at H = 32 round 512 chunks of conv 1 down to 410, 992
+// keep 512): what a workspace for "up to M items" is sized by
+int wgrad_nchunk(int layer, int M, int cout, int cin, bool bound) {
   // one workgroup per CU (LDS-bound): at most 256 / tiles chunks, each of >= 64 rows; partial
   // blocks cost a write + a read of cout*ks*cin floats per chunk (layer 6: the fc, geometry of 5)
   const LayerGeom gm = layer_geom(layer == 6 ? 5 : layer);
@@ -1867,7 +1880,7 @@ int wgrad_nchunk(int layer, int M, int cout, int cin) {
     const long rmax = ((long)(kWgItems - 3) * gm.lp * gm.pool) / kW16Rows * kW16Rows;
     if (n < (rows + rmax - 1) / rmax) n = (rows + rmax - 1) / rmax;
     if (n < 1) n = 1;
-    n = (rows + w16_rows_per_chunk(rows, (int)n) - 1) / w16_rows_per_chunk(rows, (int)n);
+    if (!bound) n = (rows + w16_rows_per_chunk(rows, (int)n) - 1) / w16_rows_per_chunk(rows, (int)n);
     return (int)(n < 1 ? 1 : n);
   }
   const long tiles = w16t_layer(layer, cin)
@@ -1908,9 +1921,35 @@ int wgrad_nchunk(int layer, int M, int cout, int cin) {
     if (n < (rows + rmax - 1) / rmax) n = (rows + rmax - 1) / rmax;
   }
   if (n < 1) n = 1;
-  if (wgrad_f16_on())  // whole stages per chunk: no chunk left empty by the rounding
+  if (wgrad_f16_on() && !bound)  // whole stages per chunk: no chunk left empty by the rounding
     n = (rows + w16_rows_per_chunk(rows, (int)n) - 1) / w16_rows_per_chunk(rows, (int)n);
   return (int)(n < 1 ? 1 : n);
+}
+
+// The kernel (WK_*) of layer `layer`'s weight gradient in a training step: layer 1 in a launch of its
+// own (launch_conv_wgrad, `src` its track table's type); layer 2 alone and layers 3..6 together in
+// launch_conv_wgrad_multi (`alone`: the only layer of its launch)
+int wgrad_kernel(int layer, int cin, int cout, int src, bool alone) {
+  if (layer == 1) {
+    if (!wgrad_f16_on()) return WK_CONV1;
+    if (src == SRC_TRACK_F16 && w1k_layer1(cin, cout)) return WK_1K;
+    return w16t_layer(1, cin) ? WK_16T : WK_16;
+  }
+  if (alone && layer == 2 && w16t_layer(2, cin)) return WK_16T;  // layer 2 alone: tap-fused + its reduce
+  return wgrad_f16_on() ? WK_MULTI_F16 : WK_MULTI_F32;
+}
+
+// dcue_debug_launch_shape: the kernel, chunk count, chunk length and last chunk's rows of that launch
+void wgrad_shape(int layer, int M, int cout, int cin, int src, bool alone, int32_t* out) {
+  const LayerGeom gm = layer_geom(layer == 6 ? 5 : layer);
+  const long rows = (long)M * gm.lp * gm.pool;
+  const int kernel = wgrad_kernel(layer, cin, cout, src, alone);
+  const int nchunk = wgrad_nchunk(layer, M, cout, cin);
+  const long rpc = wgrad_chunk_rows(kernel, rows, nchunk);
+  out[0] = kernel;
+  out[1] = nchunk;
+  out[2] = (int32_t)rpc;
+  out[3] = (int32_t)(rows - (nchunk - 1) * rpc);
 }
 
 template <int L, int SRCX>
@@ -1928,8 +1967,7 @@ static int wgrad_layer(const WgradArgs& a0, int nchunk, hipStream_t s) {
   }
   WgradArgs a = a0;
   const long rows = (long)a.M * R;
-  const long rpc = (rows + nchunk - 1) / nchunk;  // the last chunk may be short; rows past it are masked
-  a.rows_per_chunk = (int)rpc;
+  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_F32, rows, nchunk);
   dim3 grid((unsigned)((gm.ks * a.cin + 127) / 128), (unsigned)((a.cout + 127) / 128), (unsigned)nchunk);
   DCUE_LAUNCH(kern, grid, dim3(256), LDS, s, a);
   DCUE_LAUNCH_CHECK();
@@ -1951,7 +1989,7 @@ static int wgrad16t_launch(const WgradArgs& a0, int nchunk, hipStream_t s) {
   WgradArgs a = a0;
   const long rows = (long)a.M * R;
   if (rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;  // 32-bit row indices
-  a.rows_per_chunk = (int)w16_rows_per_chunk(rows, nchunk);
+  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_16T, rows, nchunk);
   if (SRCX != SRC_ACT && R >= kW16Rows && a.rows_per_chunk / R + 3 > kWgItems) return DCUE_ERR_INVALID;
   const unsigned ot = (unsigned)((a.cout + kW16tO - 1) / kW16tO);
   DCUE_LAUNCH(kern, dim3(ot * (unsigned)nchunk), dim3(kW16tThreads), LDS, s, a);
@@ -1973,7 +2011,7 @@ static int wgrad1k_launch(const WgradArgs& a0, int nchunk, hipStream_t s) {
   WgradArgs a = a0;
   const long rows = (long)a.M * R;
   if (rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;  // 32-bit row indices
-  a.rows_per_chunk = (int)w16_rows_per_chunk(rows, nchunk);
+  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_1K, rows, nchunk);
   if (a.rows_per_chunk / R + 3 > kWgItems) return DCUE_ERR_INVALID;  // (wgrad_nchunk keeps it in range)
   const unsigned tiles = (unsigned)(((a.cout + kW1kO - 1) / kW1kO) * gm.ks);
   DCUE_LAUNCH(kern, dim3(tiles * (unsigned)nchunk), dim3(kW1kThreads), LDS, s, a);
@@ -1985,10 +2023,12 @@ template <int L, int SRCX>
 static int wgrad16_layer(const WgradArgs& a0, int nchunk, hipStream_t s) {
   constexpr LayerGeom gm = layer_geom(L);
   constexpr int R = gm.lp * gm.pool;
-  if constexpr (L == 1 && SRCX == SRC_TRACK_F16)
-    if (w1k_layer1(a0.cin, a0.cout)) return wgrad1k_launch(a0, nchunk, s);
-  if constexpr (L == 1)
-    if (w16t_layer(1, a0.cin)) return wgrad16t_launch<1, SRCX>(a0, nchunk, s);
+  if constexpr (L == 1) {
+    const int kernel = wgrad_kernel(1, a0.cin, a0.cout, SRCX, true);
+    if constexpr (SRCX == SRC_TRACK_F16)
+      if (kernel == WK_1K) return wgrad1k_launch(a0, nchunk, s);
+    if (kernel == WK_16T) return wgrad16t_launch<1, SRCX>(a0, nchunk, s);
+  }
   auto kern = k_conv_wgrad16<SRCX, gm.ks, gm.pad, gm.lin, R, gm.pool, gm.lp, L == 1>;
   static bool attr = false;
   if (!attr) {
@@ -1999,7 +2039,7 @@ static int wgrad16_layer(const WgradArgs& a0, int nchunk, hipStream_t s) {
   WgradArgs a = a0;
   const long rows = (long)a.M * R;
   if (rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;  // 32-bit row indices
-  a.rows_per_chunk = (int)w16_rows_per_chunk(rows, nchunk);
+  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_16, rows, nchunk);
   dim3 grid((unsigned)((gm.ks * a.cin + 127) / 128), (unsigned)((a.cout + 127) / 128), (unsigned)nchunk);
   DCUE_LAUNCH(kern, grid, dim3(256), kW16LdsB, s, a);
   DCUE_LAUNCH_CHECK();
@@ -2132,7 +2172,7 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
   w.start[0] = 0;
   w.rstart[0] = 0;
   if (w.n < 1 || w.n > kWgradMultiMax) return DCUE_ERR_INVALID;
-  if (w.n == 1 && w.layer[0] == 2 && w16t_layer(2, w.a[0].cin)) {  // layer 2 alone: tap-fused + its reduce
+  if (w.layer[0] == 2 && wgrad_kernel(2, w.a[0].cin, w.a[0].cout, SRC_ACT, w.n == 1) == WK_16T) {  // layer 2 alone
     const WgradArgs& a = w.a[0];
     TRY((wgrad16t_launch<2, SRC_ACT>(a, w.nchunk[0], s)));
     w.rstart[1] = (int)(((long)a.cout * 4 * a.cin + 127) / 128 + (a.cout + 127) / 128);
@@ -2147,7 +2187,7 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
     if (a.cin % 32 || a.cout % 4) return DCUE_ERR_UNSUPPORTED;
     const long rows = (long)a.M * gm.lp * gm.pool;
     if (f16 && rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;
-    a.rows_per_chunk = (int)(f16 ? w16_rows_per_chunk(rows, w.nchunk[j]) : (rows + w.nchunk[j] - 1) / w.nchunk[j]);
+    a.rows_per_chunk = (int)wgrad_chunk_rows(f16 ? WK_MULTI_F16 : WK_MULTI_F32, rows, w.nchunk[j]);
     w.kt[j] = (gm.ks * a.cin + 127) / 128;
     w.ot[j] = (a.cout + 127) / 128;
     w.start[j + 1] = w.start[j] + w.kt[j] * w.ot[j] * w.nchunk[j];

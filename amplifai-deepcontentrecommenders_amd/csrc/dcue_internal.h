@@ -176,6 +176,23 @@ struct WgradMulti {
   int rstart[kWgradMultiMax + 1];     // reduce block ranges
 };
 int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s);
+// the weight-gradient kernels (conv_wgrad.hip wgrad_kernel; dcue_debug_launch_shape reports the number)
+enum {
+  WK_16T = 0,        // k_conv_wgrad16t: tap-fused split-f16 (layers 1, 2 with 128 input channels)
+  WK_16 = 1,         // k_conv_wgrad16: kc-tiled split-f16, one layer per launch
+  WK_F32 = 2,        // k_conv_wgrad: f32 MFMA, one layer per launch
+  WK_CONV1 = 3,      // k_conv1_wgrad: conv 1 on f32 MFMA over xhat0
+  WK_MULTI_F16 = 4,  // k_conv_wgrad16_multi: the multi-layer launch, kc-tiled split-f16
+  WK_MULTI_F32 = 5,  // k_conv_wgrad_multi: the multi-layer launch, f32 MFMA
+  WK_1K = 6          // k_conv_wgrad1k: conv 1, one tap per workgroup (DCUE_W1K=1)
+};
+int wgrad_kernel(int layer, int cin, int cout, int src, bool alone);
+// dcue_debug_launch_shape's records (include/dcue.h): 5 words per k_conv_rows launch, 4 per weight
+// gradient, 5 for the score / item-gradient tail
+void conv_fwd_shape(int layer, int kc, int nout, int M, int32_t* out);
+void conv_dgrad_shape(int layer, int kc, int nout, int M, int32_t* out);
+void wgrad_shape(int layer, int M, int cout, int cin, int src, bool alone, int32_t* out);
+void tail_shape(int n_neg, int n_items, int d, bool gather, bool copy_lists, bool fc, int32_t* out);
 // weight gradients on split-f16 MFMA (DCUE_WGRAD_F16=0: the f32-MFMA kernels)
 bool wgrad_f16_on();
 
@@ -186,7 +203,7 @@ int launch_conv_wgrad(int layer, int src, const WgradArgs& a, int nchunk, hipStr
 // layout, bn0's batch statistics finalized from its accumulators (layer 1's wgrad reads it from `xsrc`)
 int launch_xhat0(int src, const void* tracks, const int32_t* item_track, int M, const unsigned long long* acc0,
                  double count, float* xhat0, hipStream_t s);
-int wgrad_nchunk(int layer, int M, int cout, int cin);
+int wgrad_nchunk(int layer, int M, int cout, int cin, bool bound = false);
 // layer 1: the pooled BN1 backward dx1[M*33][cout] that k_conv1_wgrad reads from `g_l` (the
 // WgradArgs of the same call, with g_l the pooled gradient)
 int launch_conv1_dx(const WgradArgs& a, float* dx1, hipStream_t s);

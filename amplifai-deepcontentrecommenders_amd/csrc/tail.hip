@@ -408,14 +408,18 @@ int launch_signal(unsigned* flag, unsigned val, hipStream_t s) {
   return DCUE_OK;
 }
 
+// k_score_fused's CPW by the copies per row, 1 + n_neg (0: the general instantiation)
+static int score_cpw(int n_neg) { return n_neg + 1 <= 16 ? 4 : n_neg + 1 <= 32 ? 8 : 0; }
+
 int launch_score_fused(const float* uf, const float* f, const dcue_batch* b, int d, float margin,
                        float* scores, float* cosv, float* norms, float* rowsum, float* du,
                        float* dfcopy, hipStream_t s, DevWait uf_wait) {
   if (d > 256 || b->n_neg > 1024 || b->n_rows > 1024) return DCUE_ERR_UNSUPPORTED;
-  if (b->n_neg + 1 <= 16)
+  const int cpw = score_cpw(b->n_neg);
+  if (cpw == 4)
     DCUE_LAUNCH(k_score_fused<4>, dim3(b->n_rows), dim3(256), 0, s, uf, f, *b, d, margin, scores, cosv,
                 norms, rowsum, du, dfcopy, uf_wait);
-  else if (b->n_neg + 1 <= 32)
+  else if (cpw == 8)
     DCUE_LAUNCH(k_score_fused<8>, dim3(b->n_rows), dim3(256), 0, s, uf, f, *b, d, margin, scores, cosv,
                 norms, rowsum, du, dfcopy, uf_wait);
   else
@@ -893,50 +897,70 @@ static int item_grad_multi(const float* dfcopy, const dcue_batch* b, int d, floa
   return DCUE_OK;
 }
 
+// The item gradient's variant. Multi-item workgroups (k_item_grad_multi) unless a gather batch has no
+// copy lists or the fc rides along at d > 128 (k_item_grad: one item per workgroup, its own copy scan)
+static bool item_grad_multi_wg(bool gather, bool copy_lists, bool fc, int d) {
+  return (!gather || copy_lists) && (!fc || d <= 128);
+}
+// W staged in LDS (64 KB per workgroup at d = 128), or read from L2 in the g5 loop
+// (DCUE_ITEMGRAD_WLDS=0: A/B diagnostic)
+static bool item_grad_wlds(bool multi, bool fc, int d) {
+  static const bool wlds_on = [] {
+    const char* e = getenv("DCUE_ITEMGRAD_WLDS");
+    return !(e && e[0] == '0');
+  }();
+  return multi ? fc && d % 4 == 0 && wlds_on : fc && d <= kItemGradWLds && d % 4 == 0;
+}
+// items per workgroup of k_item_grad_multi: many items (catalogue M = B(1+N)): 16; a few hundred: 4;
+// in-batch M = B = 64: one item per workgroup (measured GPU-only, A/B: 3 us under four per workgroup)
+// (DCUE_ITEMGRAD_IT = 1, 2, 4 or 16 forces one: A/B diagnostic)
+static int item_grad_it(int n_items) {
+  static const int forced = [] {
+    const char* e = getenv("DCUE_ITEMGRAD_IT");
+    return e ? atoi(e) : 0;
+  }();
+  if (forced == 1 || forced == 2 || forced == 4 || forced == 16) return forced;
+  return n_items >= 512 ? 16 : n_items >= 256 ? 4 : 1;
+}
+
+// dcue_debug_launch_shape: k_score_fused's CPW, the item-gradient kernel (0: k_item_grad_multi, 1:
+// k_item_grad), its items per workgroup, WLDS, and the items of its last workgroup
+void tail_shape(int n_neg, int n_items, int d, bool gather, bool copy_lists, bool fc, int32_t* out) {
+  const bool multi = item_grad_multi_wg(gather, copy_lists, fc, d);
+  const int it = multi ? item_grad_it(n_items) : 1;
+  out[0] = score_cpw(n_neg);
+  out[1] = multi ? 0 : 1;
+  out[2] = it;
+  out[3] = item_grad_wlds(multi, fc, d) ? 1 : 0;
+  out[4] = n_items - (n_items + it - 1) / it * it + it;
+}
+
 int launch_item_grad(const float* dfcopy, const dcue_batch* b, int d, float* df, const float* fcW, float* g5,
                      unsigned long long* acc5, const float* y5, const float* mean5, const float* invstd5,
                      const float* rowsum, float* loss, const int32_t* copy_ptr, const int32_t* copy_idx,
                      unsigned* g5max, unsigned* dfmax, hipStream_t s) {
   if (d > 256 || (rowsum && b->n_rows > 1024)) return DCUE_ERR_UNSUPPORTED;
   const bool gather = b->layout == DCUE_LAYOUT_GATHER;
-  if ((!gather || copy_ptr) && (!fcW || d <= 128)) {  // multi-item workgroups
+  if (item_grad_multi_wg(gather, copy_ptr != nullptr, fcW != nullptr, d)) {  // multi-item workgroups
     const ItemGradFc fc = {rowsum, loss, fcW, g5, acc5, y5, mean5, invstd5, g5max, dfmax};
-    // W staged in LDS (64 KB per workgroup at d = 128), or read from L2 in the g5 loop
-    // (DCUE_ITEMGRAD_WLDS=0: A/B diagnostic)
-    static const bool wlds_on = [] {
-      const char* e = getenv("DCUE_ITEMGRAD_WLDS");
-      return !(e && e[0] == '0');
-    }();
-    const bool wlds = fcW && d % 4 == 0 && wlds_on;
+    const bool wlds = item_grad_wlds(true, fcW != nullptr, d);
     const size_t lds = wlds ? sizeof(float) * d * d : 0;
-    // many items (catalogue M = B(1+N)): 16 per workgroup; a few (in-batch M = B): 4
-    // (DCUE_ITEMGRAD_IT = 1, 2, 4 or 16 forces one: A/B diagnostic)
-    static const int forced = [] {
-      const char* e = getenv("DCUE_ITEMGRAD_IT");
-      return e ? atoi(e) : 0;
-    }();
-    if (forced == 1)
-      return wlds ? item_grad_multi<1, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
-                  : item_grad_multi<1, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
-    if (forced == 2)
+    const int it = item_grad_it(b->n_items);
+    if (it == 2)
       return wlds ? item_grad_multi<2, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
                   : item_grad_multi<2, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
-    if (forced == 4)
-      return wlds ? item_grad_multi<4, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
-                  : item_grad_multi<4, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
-    if (b->n_items >= 512 || forced == 16)
+    if (it == 16)
       return wlds ? item_grad_multi<16, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
                   : item_grad_multi<16, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
-    if (b->n_items >= 256)
+    if (it == 4)
       return wlds ? item_grad_multi<4, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
                   : item_grad_multi<4, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
-    // in-batch M = B = 64: one item per workgroup (measured GPU-only, A/B: 3 us under four per workgroup)
     return wlds ? item_grad_multi<1, true>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s)
                 : item_grad_multi<1, false>(dfcopy, b, d, df, copy_ptr, copy_idx, fc, lds, s);
   }
   if (b->layout == DCUE_LAYOUT_GATHER && (long)b->n_rows * b->n_neg + 1 > kItemGradCap) return DCUE_ERR_UNSUPPORTED;
   const ItemGradFc fc = {rowsum, loss, fcW, g5, acc5, y5, mean5, invstd5, g5max, dfmax};
-  if (fcW && d <= kItemGradWLds && d % 4 == 0) {
+  if (item_grad_wlds(false, fcW != nullptr, d)) {
     const size_t lds = sizeof(float) * d * d;
     static bool attr = false;
     if (!attr) {

@@ -214,6 +214,8 @@ _SIGS = {
     "dcue_debug_poison": ([ctypes.c_int32], ctypes.c_int),
     "dcue_debug_fail_flags": ([_P], ctypes.c_int),
     "dcue_debug_raise_fail_flags": ([ctypes.c_uint32], ctypes.c_int),
+    "dcue_debug_launch_shape": ([ctypes.POINTER(Dims), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                 ctypes.c_int32, _P, ctypes.c_int32], ctypes.c_int),
 }
 
 _lib = None
@@ -391,6 +393,29 @@ def workspace_bytes(dims, max_rows, max_neg, max_items):
     check(lib().dcue_workspace_bytes(ctypes.byref(dims), max_rows, max_neg, max_items, ctypes.byref(n)),
           "dcue_workspace_bytes")
     return n.value
+
+
+LAUNCH_SHAPE_WORDS = 74  # DCUE_LAUNCH_SHAPE_WORDS
+WGRAD_KERNELS = ("wgrad16t", "wgrad16", "wgrad_f32", "conv1_wgrad", "multi_f16", "multi_f32", "wgrad1k")
+
+
+def launch_shape(dims, layout, B, N, M):
+    """The kernel variants a training step of this shape launches (dcue_debug_launch_shape; host
+    only, no GPU needed), as a dict: "fwd" {layer: (TW, DEEP, f16, last_rows, spans_items)} for conv
+    1..5, "dgrad" the same for layers 2..5, "wgrad" {layer: (kernel, nchunk, rows_per_chunk,
+    last_chunk_rows)} for layers 1..6 (kernel a WGRAD_KERNELS name, None where the fc is a plain
+    GEMM), "tail" (CPW, item-gradient kernel, IT, WLDS, items of the last workgroup)."""
+    buf = (ctypes.c_int32 * LAUNCH_SHAPE_WORDS)()
+    check(lib().dcue_debug_launch_shape(ctypes.byref(dims), layout, B, N, M, ctypes.cast(buf, _P),
+                                        LAUNCH_SHAPE_WORDS), "dcue_debug_launch_shape")
+    w = list(buf)
+    wg = {}
+    for l in range(1, 7):
+        k, nch, rpc, last = w[45 + 4 * (l - 1):45 + 4 * l]
+        wg[l] = (WGRAD_KERNELS[k] if k >= 0 else None, nch, rpc, last)
+    return {"fwd": {l: tuple(w[5 * (l - 1):5 * l]) for l in range(1, 6)},
+            "dgrad": {l: tuple(w[25 + 5 * (l - 2):25 + 5 * (l - 1)]) for l in range(2, 6)},
+            "wgrad": wg, "tail": tuple(w[69:74])}
 
 
 def debug_delay(site, microseconds):

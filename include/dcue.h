@@ -195,6 +195,8 @@ int dcue_param_layout(const dcue_dims* dims, int64_t* offsets_host);
 /* offsets[2*DCUE_N_BN+1]: running_mean(l), running_var(l) for l = 0..5 */
 int dcue_bn_layout(const dcue_dims* dims, int64_t* offsets_host);
 int dcue_wpack_floats(const dcue_dims* dims, int64_t* n_floats_host);
+/* Bytes of a workspace for batches of up to max_rows rows, max_neg negatives and max_items items: never
+ * smaller than for any smaller batch, so one sized for the largest batch serves every smaller one. */
 int dcue_workspace_bytes(const dcue_dims* dims, int32_t max_rows, int32_t max_neg,
                          int32_t max_items, size_t* bytes_host);
 /* Byte offsets inside a workspace carved for (B, N, M) of the forward outputs a train/eval
@@ -442,6 +444,24 @@ int dcue_debug_poison(int32_t on);
 int dcue_debug_fail_flags(uint32_t* flags_host);
 /* ORs `bits` into the current device's fail word (tests: a forced flag must fail the bench line; ABI 16). */
 int dcue_debug_raise_fail_flags(uint32_t bits);
+/* Which kernel variants a training step of this shape launches (added under ABI 17; host only: no
+ * device call, works without a GPU). The launchers pick tilings, split-K partitions and kernels from
+ * the item count M (and the score kernel from N); this reports those picks from the very functions
+ * the launches call, so a test can tell which variants its shapes reach (tests/test_launch_shapes_cpu.py).
+ * layout, B, N, M as in dcue_batch (catalogue: M = B(1+N); gather: M >= B, copy lists as the step's);
+ * the track table is taken as fp16. out_host gets DCUE_LAUNCH_SHAPE_WORDS int32 words (cap: its size):
+ *   [0, 25)   conv forward 1..5, 5 words each: TW (row tiles per workgroup), DEEP, split-f16,
+ *             rows of the last workgroup (M R mod 16 TW; 0: full), a workgroup spans two items
+ *   [25, 45)  input gradient of layers 2..5, the same 5 words
+ *   [45, 69)  weight gradient of layers 1..6 (6: the fc), 4 words each: kernel (0 k_conv_wgrad16t
+ *             tap-fused split-f16, 1 k_conv_wgrad16 kc-tiled split-f16, 2 k_conv_wgrad f32, 3
+ *             k_conv1_wgrad, 4 / 5 the multi-layer launch split-f16 / f32, 6 k_conv_wgrad1k; -1: none,
+ *             the res / text towers' fc), nchunk, rows_per_chunk, rows of the last chunk
+ *   [69, 74)  k_score_fused's CPW (0: the general one), item-gradient kernel (0 k_item_grad_multi, 1
+ *             k_item_grad), its items per workgroup IT, WLDS, items of its last workgroup */
+#define DCUE_LAUNCH_SHAPE_WORDS 74
+int dcue_debug_launch_shape(const dcue_dims* dims, int32_t layout, int32_t B, int32_t N, int32_t M,
+                            int32_t* out_host, int32_t cap);
 
 /* ------------------------------------------------- data-parallel gradient exchange (RCCL) */
 /* One process per GPU; users are sharded over the ranks, so the only exchange of a step is the
