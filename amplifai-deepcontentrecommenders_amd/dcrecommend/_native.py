@@ -120,6 +120,11 @@ COMM_F32, COMM_U64 = 0, 1  # dcue_host_allreduce_fn dtypes
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32)
 RANK_SPLIT, RANK_SINGLE = 0, 1
 TOPK_MAX_K = 128  # DCUE_TOPK_MAX_K
+# dcue_topk_metrics (added under ABI 17): cutoffs per call, metrics per cutoff and their slots, flag bits
+TOPK_METRICS_MAX_CUTOFFS = 8
+TOPK_N_METRICS = 6
+TOPK_METRIC_NAMES = ("precision", "recall", "ndcg", "map", "mrr", "hit")  # DCUE_TOPK_METRIC_* order
+TOPK_FLAG_NO_TRUTH, TOPK_FLAG_BAD_INDEX = 1, 2
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd")
@@ -200,6 +205,10 @@ _SIGS = {
     "dcue_topk": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P,
                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P],
                   ctypes.c_int),
+    "dcue_topk_metrics": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P,
+                           ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_topk_metrics_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P, _P, _P],
+                               ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),

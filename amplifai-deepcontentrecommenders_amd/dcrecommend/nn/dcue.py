@@ -587,6 +587,57 @@ class DCUE(Trainer):
         feat = self._item_feat_by_index()
         return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
 
+    # ------------------------------------------------------------------ list quality
+    def _topk_metrics(self, ds):
+        """rank.TopKMetrics per dataset, cached as _topk caches its lists, and the user rows with a
+        non-empty truth row. Truth = the all-split interaction row restricted to the candidates."""
+        key = ("topk_metrics", id(ds))
+        if key not in self._evals:
+            mask = self._cand_mask(ds)
+            src = ds if ds is not None else self.train_data
+            if src is None:
+                raise RuntimeError("evaluate_topk needs the interactions: pass dataset= (any split's "
+                                   "dataset holds the all-split matrix) or fit() first")
+            ptr, idx = src.user_item_csr()
+            keep = mask[idx] != 0
+            kept = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+            ptr, idx = kept[ptr], idx[keep]
+            self._evals[key] = (rank.TopKMetrics(ptr, idx, self.device, cand_mask=mask),
+                                np.flatnonzero(np.diff(ptr) > 0).astype(np.int64))
+        return self._evals[key]
+
+    def evaluate_topk(self, dataset=None, ks=(10, 50, 100), users=None, per_user=False):
+        """Top-K ranking quality of the current factors: {"precision@K", "recall@K", "ndcg@K", "map@K",
+        "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} (include/dcue.h dcue_topk_metrics
+        has the definitions). Candidates are the dataset's (or loader's) split songs with audio, or
+        every song with audio; a user's truth is every candidate the user interacted with in any
+        split -- with a song-split dataset the held-out songs, none of which training saw. users:
+        user ids (an unknown one raises KeyError); default every user with a non-empty truth row, in
+        index order. Users without truth are left out of the means; n_users counts the others.
+        per_user adds "users" (the ids), "per_user" (numpy [n, len(ks), 6], slots in
+        _native.TOPK_METRIC_NAMES order) and "flags" (bit 0: no truth). Every list is ranked and
+        scored on the GPU (dcue_topk, then dcue_topk_metrics on its device output); the reference has
+        only DCUE.score's sampled AUC / mAP."""
+        ks = rank.check_cutoffs(ks)
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        src = self._index_source(ds)
+        ev, with_truth = self._topk_metrics(ds)
+        if users is None:
+            rows = with_truth
+            users = [src.userindex2userid[int(r)] for r in rows] if per_user else None
+        else:
+            users = list(users)
+            rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
+        res = ev.evaluate(self.user_factors, self._item_feat_by_index(), rows, ks, per_query=per_user)
+        out = {"n_users": res["n_evaluated"]}
+        for name in nat.TOPK_METRIC_NAMES + ("coverage",):
+            for i, k in enumerate(ks):
+                out["%s@%d" % (name, k)] = float(res[name][i])
+        if per_user:
+            out.update(users=users, per_user=res["per_query"], flags=res["flags"])
+        return out
+
     # ------------------------------------------------------------------ unseen users
     def _cand_mask(self, ds):
         """The candidates of _topk: songs with audio (the others have zero factors), in the split."""

@@ -9,6 +9,9 @@ the host, and every sampled query is ranked on the GPU in one call.
 TopK (dcue_topk) is the serving counterpart: the k best candidates per query, with a candidate mask
 and a per-query exclusion CSR, fused so that the score matrix is never written.
 
+TopKMetrics (dcue_topk_metrics) says how good TopK's lists are: Precision / Recall / NDCG / MAP / MRR /
+HitRate at several cutoffs and catalogue coverage against held-out truth rows, on the device lists.
+
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
@@ -236,6 +239,141 @@ class TopK(_Workspace):
         if bad.any():
             raise _nonfinite_error(queries, bad)
         return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
+
+
+def check_cutoffs(ks):
+    """The sorted distinct cutoffs of `ks` as a list of ints; ValueError naming the limit otherwise."""
+    ks = sorted({int(k) for k in ks})
+    if not ks:
+        raise ValueError("ks is empty: at least 1 cutoff is needed")
+    if len(ks) > nat.TOPK_METRICS_MAX_CUTOFFS:
+        raise ValueError("at most %d cutoffs per call, got %d" % (nat.TOPK_METRICS_MAX_CUTOFFS, len(ks)))
+    if ks[0] < 1 or ks[-1] > nat.TOPK_MAX_K:
+        raise ValueError("cutoffs must be in 1..%d, got %s" % (nat.TOPK_MAX_K, ks))
+    return ks
+
+
+class TopKMetrics(_Workspace):
+    """Precision / Recall / NDCG / MAP / MRR / HitRate at several cutoffs and catalogue coverage of the
+    lists of one recommendation setting, computed where dcue_topk leaves them (include/dcue.h
+    dcue_topk_metrics / dcue_topk_metrics_mean): no list is copied to the host, no score matrix exists.
+
+    truth_ptr [n_query_rows + 1] int64 / truth_idx int32: per query row, the sorted held-out candidates
+    (dcue_topk's exclusion format); excl_ptr / excl_idx, cand_mask, n_cand: as TopK, which it owns for
+    the lists."""
+
+    def __init__(self, truth_ptr, truth_idx, device, excl_ptr=None, excl_idx=None, cand_mask=None, n_cand=None):
+        self.device = torch.device(device)
+        self.topk = TopK(excl_ptr, excl_idx, cand_mask, self.device, n_cand=n_cand)
+        self.cand_mask, self.n_cand = self.topk.cand_mask, self.topk.n_cand
+        truth_ptr = np.ascontiguousarray(truth_ptr, dtype=np.int64)
+        truth_idx = np.ascontiguousarray(truth_idx, dtype=np.int32)
+        if len(truth_ptr) < 2 or truth_ptr[0] != 0 or truth_ptr[-1] != len(truth_idx) or np.any(np.diff(truth_ptr) < 0):
+            raise ValueError("truth_ptr is not a CSR pointer array over truth_idx")
+        self.n_query_rows = len(truth_ptr) - 1
+        if self.topk.excl_ptr is not None and self.topk.excl_ptr.numel() != len(truth_ptr):
+            raise ValueError("the exclusion CSR has %d rows, the truth CSR %d"
+                             % (self.topk.excl_ptr.numel() - 1, self.n_query_rows))
+        self.truth_ptr, self.truth_idx = _upload_csr(truth_ptr, truth_idx, self.device)
+
+    def _cutoffs(self, ks):
+        ks = check_cutoffs(ks)
+        return ks, (ctypes.c_int32 * len(ks))(*ks)
+
+    def _metrics_into(self, idx, count, q, cut, m, out, flags, exposure):
+        """dcue_topk_metrics on device lists, writing out [n, m, 6] / flags [n] (views of the caller's
+        buffers) and accumulating into exposure (or None)."""
+        nat.check(nat.lib().dcue_topk_metrics(
+            nat.ptr(idx), nat.ptr(count), int(q.numel()), int(idx.shape[1]), nat.ptr(q), nat.ptr(self.truth_ptr),
+            nat.ptr(self.truth_idx), self.n_query_rows, self.n_cand, ctypes.cast(cut, ctypes.c_void_p), m,
+            nat.ptr(out), nat.ptr(flags), nat.ptr(exposure), nat.stream_handle(self.device)), "dcue_topk_metrics")
+
+    def _device_lists(self, idx, count, queries):
+        nat.require_gpu(idx, "idx")
+        nat.require_gpu(count, "count")
+        if idx.dim() != 2 or idx.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() != idx.shape[0]:
+            raise ValueError("idx must be int32 [n, k] and count int32 [n]")
+        if not 1 <= idx.shape[1] <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, idx.shape[1]))
+        q = torch.as_tensor(np.asarray(queries, dtype=np.int32)).to(self.device)
+        if q.numel() != idx.shape[0]:
+            raise ValueError("%d queries for %d lists" % (q.numel(), idx.shape[0]))
+        return idx.contiguous(), count.contiguous(), q
+
+    def metrics_raw(self, idx, count, queries, ks, exposure=None):
+        """(metrics float64 [n, m, 6], flags int32 [n]) device tensors for caller-supplied device lists
+        (idx int32 [n, k], count int32 [n], as dcue_topk writes them). exposure: an int32 [m, n_cand]
+        device tensor to accumulate into, or None."""
+        ks, cut = self._cutoffs(ks)
+        idx, count, q = self._device_lists(idx, count, queries)
+        if ks[-1] > idx.shape[1]:
+            raise ValueError("cutoff %d is beyond the lists' k = %d" % (ks[-1], idx.shape[1]))
+        n, m = int(q.numel()), len(ks)
+        out = torch.zeros((max(n, 1), m, nat.TOPK_N_METRICS), dtype=torch.float64, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        if n:
+            self._metrics_into(idx, count, q, cut, m, out, flags, exposure)
+        return out[:n], flags[:n]
+
+    def new_exposure(self, m):
+        return torch.zeros((m, self.n_cand), dtype=torch.int32, device=self.device)
+
+    def mean_raw(self, metrics, flags, exposure=None):
+        """(mean float64 [m, 6], coverage float64 [m] or None, n_evaluated int32 [1]) device tensors:
+        dcue_topk_metrics_mean over metrics [n, m, 6] / flags [n]."""
+        n, m = int(metrics.shape[0]), int(metrics.shape[1])
+        mean = torch.zeros((m, nat.TOPK_N_METRICS), dtype=torch.float64, device=self.device)
+        cov = torch.zeros(m, dtype=torch.float64, device=self.device) if exposure is not None else None
+        n_eval = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if n == 0:  # (an empty tensor's address may be null)
+            metrics = torch.zeros((1, m, nat.TOPK_N_METRICS), dtype=torch.float64, device=self.device)
+            flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().dcue_topk_metrics_mean(
+            nat.ptr(metrics.contiguous()), nat.ptr(flags.contiguous()), n, m, nat.ptr(exposure),
+            nat.ptr(self.cand_mask), self.n_cand, nat.ptr(mean), nat.ptr(cov), nat.ptr(n_eval),
+            nat.stream_handle(self.device)), "dcue_topk_metrics_mean")
+        return mean, cov, n_eval
+
+    def evaluate(self, query_feat, cand_feat, queries, ks, query_batch=None, per_query=False):
+        """{"ks", "n_evaluated", "precision", "recall", "ndcg", "map", "mrr", "hit", "coverage"}: each
+        metric a float64 array over the cutoffs, the mean over the queries with a non-empty truth row;
+        per_query adds "per_query" (numpy [n, m, 6], slots in nat.TOPK_METRIC_NAMES order) and "flags".
+        Query batches go through TopK.topk_raw with k = max(ks) and dcue_topk_metrics on its device
+        tensors; one dcue_topk_metrics_mean call ends it. The result does not depend on query_batch.
+
+        Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
+        infinite, as TopK.topk does."""
+        ks, cut = self._cutoffs(ks)
+        queries = np.asarray(queries, dtype=np.int64).reshape(-1)
+        n, m, k = len(queries), len(ks), ks[-1]
+        if self.topk.excl_ptr is None and query_feat.shape[0] != self.n_query_rows:
+            raise ValueError("query factors have %d rows, the truth CSR %d" % (query_feat.shape[0], self.n_query_rows))
+        qb = int(self.topk.DEFAULT_QUERY_BATCH if query_batch is None else query_batch)
+        if qb < 1:
+            raise ValueError("query_batch must be positive")
+        out = torch.zeros((max(n, 1), m, nat.TOPK_N_METRICS), dtype=torch.float64, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        nonfinite = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        exposure = self.new_exposure(m)
+        for q0 in range(0, n, qb):
+            part = queries[q0:q0 + qb]
+            idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb)
+            q = torch.as_tensor(part.astype(np.int32)).to(self.device)
+            self._metrics_into(idx, count, q, cut, m, out[q0:], flags[q0:], exposure)
+            nonfinite[q0:q0 + len(part)] = tflags
+        bad = (nonfinite[:n].cpu().numpy() & 2).astype(bool)
+        if bad.any():
+            raise _nonfinite_error(queries, bad)
+        mean, cov, n_eval = self.mean_raw(out[:n], flags[:n], exposure)
+        mean = mean.cpu().numpy()
+        res = {"ks": list(ks), "n_evaluated": int(n_eval.cpu().numpy()[0])}
+        for s, name in enumerate(nat.TOPK_METRIC_NAMES):
+            res[name] = mean[:, s].copy()
+        res["coverage"] = cov.cpu().numpy()
+        if per_query:
+            res["per_query"] = out[:n].cpu().numpy()
+            res["flags"] = flags[:n].cpu().numpy()
+        return res
 
 
 def histories_csr(rows):

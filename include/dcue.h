@@ -673,6 +673,66 @@ int dcue_foldin_negatives(int64_t n_cand, const uint8_t* cand_mask, const int64_
                           const int32_t* hist_idx, int32_t n_users, int64_t row0,
                           const dcue_foldin_config* cfg, int32_t step, int32_t* out_neg, void* stream);
 
+/* ------------------------------------------------------- top-K ranking metrics (added under ABI 17) */
+/* How good the lists dcue_topk serves are: Precision / Recall / NDCG / MAP / MRR / HitRate at up to
+ * DCUE_TOPK_METRICS_MAX_CUTOFFS cutoffs per query, and the exposure counts catalogue coverage is read
+ * from, computed on the lists where dcue_topk left them (no list goes to the host, no score matrix).
+ * The reference has no counterpart (its only quality numbers are DCUE.score's AUC / mAP).
+ *   idx [n_queries][k], count[n_queries]: dcue_topk's out_idx / out_count: list L[0..c), c = count
+ *     clamped to 0..k, best first. Entries at j >= c (the -1 padding) are never read.
+ *   queries[n_queries]: the query row of each list (repeats allowed; each occurrence counts).
+ *   truth_ptr[n_query_rows+1], truth_idx: CSR over query rows of the held-out items T of the query,
+ *     t = |T|, each row sorted, no repeats -- dcue_topk's exclusion format.
+ *   cutoffs_host[n_cutoffs] (HOST memory): 1 <= k_1 < ... < k_m <= k, 1 <= m <= 8.
+ * With h_j = [L[j] in T] for j < c, h_j = 0 for j >= c, and H_j = h_0 + ... + h_j, at a cutoff K:
+ *   DCUE_TOPK_METRIC_PRECISION  H_{K-1} / K (K, not min(K, c))
+ *   DCUE_TOPK_METRIC_RECALL     H_{K-1} / t
+ *   DCUE_TOPK_METRIC_NDCG       (sum_{j<K} h_j / log2(j+2)) / (sum_{j<min(K,t)} 1 / log2(j+2))
+ *   DCUE_TOPK_METRIC_MAP        (sum_{j<K} h_j H_j / (j+1)) / min(K, t)
+ *   DCUE_TOPK_METRIC_MRR        1 / (j*+1), j* the first j < K with h_j = 1; 0 if there is none
+ *   DCUE_TOPK_METRIC_HIT        [H_{K-1} > 0]
+ * all in fp64. out_metrics [n_queries][n_cutoffs][DCUE_TOPK_N_METRICS]; a query's numbers are a
+ * function of its list and its truth row alone (fixed summation order), so they do not depend on how
+ * a caller batches its queries.
+ *   out_flags[q] bit 0: the truth row is empty; bit 1: an entry L[j], j < c, lies outside
+ *     [0, n_cand) (each entry is range-checked before it addresses anything), or queries[q] lies
+ *     outside [0, n_query_rows). A flagged query's metrics are 0, and it is left out of every mean
+ *     and of the exposure counts.
+ *   exposure (nullable) int32 [n_cutoffs][n_cand]: position j < k_m of an evaluated (unflagged) query
+ *     adds 1 to exposure[i][L[j]], i the first cutoff with j < k_i (integer atomics: deterministic).
+ *     The kernel accumulates; the caller zeroes the buffer before the first call of an evaluation.
+ * dcue_topk_metrics_mean: out_mean [n_cutoffs][DCUE_TOPK_N_METRICS] = the arithmetic mean of `metrics`
+ * over the queries with flags == 0, *out_n_evaluated their number (means 0 where it is 0). With
+ * `exposure`, out_coverage[i] = (candidates c with exposure[0..i][c] not all zero) / (candidates with a
+ * non-zero cand_mask byte; n_cand with a null mask) -- the share of the catalogue that appears in the
+ * first k_i entries of at least one evaluated query; out_coverage is null exactly when exposure is.
+ * The summation order depends on n_queries and n_cutoffs only (one workgroup, fixed chunks, no
+ * floating-point atomics): the means are bit-identical however `metrics` was filled.
+ * Both calls validate every argument on the host before their first device call (DCUE_ERR_INVALID: a
+ * null required pointer, k outside 1..DCUE_TOPK_MAX_K, n_cutoffs outside 1..8, cutoffs not strictly
+ * ascending / below 1 / above k, n_cand <= 0, n_query_rows <= 0, n_queries < 0; DCUE_ERR_UNSUPPORTED:
+ * n_cand beyond dcue_topk's bound). n_queries == 0 is DCUE_OK (the means are 0, *out_n_evaluated 0).
+ * Both are asynchronous on `stream`. */
+#define DCUE_TOPK_METRICS_MAX_CUTOFFS 8
+#define DCUE_TOPK_N_METRICS 6
+#define DCUE_TOPK_METRIC_PRECISION 0
+#define DCUE_TOPK_METRIC_RECALL 1
+#define DCUE_TOPK_METRIC_NDCG 2
+#define DCUE_TOPK_METRIC_MAP 3
+#define DCUE_TOPK_METRIC_MRR 4
+#define DCUE_TOPK_METRIC_HIT 5
+#define DCUE_TOPK_FLAG_NO_TRUTH 1
+#define DCUE_TOPK_FLAG_BAD_INDEX 2
+int dcue_topk_metrics(const int32_t* idx, const int32_t* count, int32_t n_queries, int32_t k,
+                      const int32_t* queries, const int64_t* truth_ptr, const int32_t* truth_idx,
+                      int64_t n_query_rows, int64_t n_cand, const int32_t* cutoffs_host,
+                      int32_t n_cutoffs, double* out_metrics, int32_t* out_flags, int32_t* exposure,
+                      void* stream);
+int dcue_topk_metrics_mean(const double* metrics, const int32_t* flags, int32_t n_queries,
+                           int32_t n_cutoffs, const int32_t* exposure, const uint8_t* cand_mask,
+                           int64_t n_cand, double* out_mean, double* out_coverage,
+                           int32_t* out_n_evaluated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,12 +9,14 @@ this is that driver for the MI355X build:
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv      # + each user's top 10
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-for new.csv
                                                   # the top 10 of users outside the training set
+  python train_dcue.py ... --eval-k 10,50,100 --eval-out metrics.json     # + top-K ranking metrics
 
 triplets: (user_id, song_id, score) by column position (datasets/dcuedataset.py:229,238);
 metadata: song_id in column 1 and a `data_mel` column of torch.save'd [128, T] tensors
 (datasets/dcueitemset.py:46,50). Arguments mirror DCUE's constructor (nn/dcue.py:47-50).
 """
 import argparse
+import json
 import os
 import sys
 import tempfile
@@ -59,7 +61,18 @@ def parse(argv=None):
                     help="columns user_id,song_id: histories of users outside the training set; their "
                          "lists (DCUE.recommend_for: fold-in, then top K) are written instead of the "
                          "training users'")
+    ap.add_argument("--eval-k", metavar="K[,K...]",
+                    help="after training, Precision / Recall / NDCG / MAP / MRR / HitRate / coverage at these "
+                         "cutoffs over the val and the test split (DCUE.evaluate_topk)")
+    ap.add_argument("--eval-out", help="JSON for --eval-k: {\"val\": {...}, \"test\": {...}}")
     args = ap.parse_args(argv)
+    if bool(args.eval_k) != bool(args.eval_out):
+        ap.error("--eval-k and --eval-out go together")
+    if args.eval_k:
+        try:
+            args.eval_k = [int(k) for k in args.eval_k.split(",")]
+        except ValueError:
+            ap.error("--eval-k takes comma-separated integers, got %r" % args.eval_k)
     if (args.recommend_k > 0) != bool(args.recommend_out):
         ap.error("--recommend-k and --recommend-out go together")
     if args.recommend_for and not args.recommend_out:
@@ -129,7 +142,19 @@ def main(argv=None):
                                   histories=histories, seed=args.seed)
         else:
             write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out)
+    if args.eval_k:
+        write_metrics(dcue, val, test, args.eval_k, args.eval_out)
     return dcue
+
+
+def write_metrics(dcue, val, test, ks, path):
+    """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs."""
+    if dcue.best_user_factors is not None:
+        dcue.insert_best_factors()
+    res = {"val": dcue.evaluate_topk(val, ks=ks), "test": dcue.evaluate_topk(test, ks=ks)}
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def write_recommendations(dcue, users, k, path, histories=None, seed=0):
