@@ -635,6 +635,7 @@ struct UserFwdArgs {
   int B, E;
   unsigned* fail;          // set when a wait for another workgroup's claim gave up (never expected)
   unsigned* sig;           // plans: +1 per workgroup once its uf rows are stored (dev_signal_wg)
+  DevWait start;           // plans: the step's start on the caller's stream (the batch's users are in)
 };
 
 // 256-thread GEMM parts per workgroup. (3 -- 768 threads, 2 GEMM-1 rounds instead of 3 -- fits the
@@ -648,6 +649,7 @@ __global__ __launch_bounds__(256 * kUfParts) void k_user_fwd(UserFwdArgs a) {
   __shared__ int64_t user_s[16];
   DCUE_KTW(0, 6);
   DCUE_KT(0, 0);
+  dev_wait(a.start);  // (before the first read of the users and of the table)
   const int t = threadIdx.x, half = t >> 8, th = t & 255;
   const int r0 = blockIdx.x * 16, nr = min(16, a.B - r0);
   if (a.emb_step) {
@@ -753,7 +755,7 @@ __global__ __launch_bounds__(256 * kUfParts) void k_user_fwd(UserFwdArgs a) {
 int user_fwd_blocks(int B) { return (B + 15) / 16; }
 
 int launch_user_fwd(const dcue_model* md, const TGemmArgs& g1, const TGemmArgs& g2, const int64_t* users, int B,
-                    hipStream_t s, unsigned* sig) {
+                    hipStream_t s, unsigned* sig, DevWait start) {
   if (g1.sak != 1 || g1.sbn == 1 || g2.sak != 1 || g2.sbn == 1 || !g1.arow || g2.arow) return DCUE_ERR_INVALID;
   UserFwdArgs a;
   a.g1 = g1; a.g2 = g2;
@@ -764,6 +766,7 @@ int launch_user_fwd(const dcue_model* md, const TGemmArgs& g1, const TGemmArgs& 
   if (!fail) return DCUE_ERR_HIP;
   a.fail = fail;
   a.sig = sig;
+  a.start = start;
   DCUE_LAUNCH(k_user_fwd, dim3((unsigned)user_fwd_blocks(B)), dim3(256 * kUfParts), 0, s, a);
   DCUE_LAUNCH_CHECK();
   return DCUE_OK;

@@ -92,7 +92,9 @@ bool& capturing_step() {
   return c;
 }
 
-ForkAfter::ForkAfter(SidePool* p, hipStream_t s, hipEvent_t* ev) : s_(s), out_(ev), e_(ring_event(p)) {
+ForkAfter::ForkAfter(SidePool* p, hipStream_t s, hipEvent_t* ev)
+    : s_(s), out_(ev), e_(ev ? ring_event(p) : nullptr) {
+  if (!ev) return;  // a point nobody waits for: nothing bound, nothing recorded
   saved_ = launch_tag();
   if (!capturing_step()) {
     launch_tag() = LaunchTag{nullptr, e_, 0, false};
@@ -109,7 +111,7 @@ void ForkAfter::restore() {
 }
 
 int ForkAfter::done() {
-  if (finished_) return DCUE_OK;
+  if (finished_ || !out_) return DCUE_OK;
   finished_ = true;
   const bool bound = armed_ && launch_tag().launches > 0 && !launch_tag().missed;
   restore();
@@ -126,6 +128,15 @@ int join_user_stream(hipStream_t s) {
   SidePool* sp = side_pool();
   if (!sp) return DCUE_ERR_HIP;
   return stream_wait(sp, s, sp->st[0]);
+}
+
+bool xq_edge_on(int group) {
+  static const bool on[3] = {
+      [] { const char* e = getenv("DCUE_XQ_START"); return !(e && e[0] == '0'); }(),
+      [] { const char* e = getenv("DCUE_XQ_FORK"); return !(e && e[0] == '0'); }(),
+      [] { const char* e = getenv("DCUE_XQ_LATE"); return !(e && e[0] == '0'); }(),
+  };
+  return group >= 0 && group < 3 && on[group];
 }
 
 int wait_point(hipStream_t to, hipEvent_t ev) {
@@ -479,7 +490,7 @@ int item_forward(const Ctx& c, const Ws& w, const dcue_tracks* t, const int32_t*
                  bool acc_cleared = false, bool stats_done = false, bool clear_bn0 = false,
                  hipEvent_t before_l2 = nullptr, const std::function<int()>* after_l1 = nullptr,
                  dcue_comm* sync_bn = nullptr, const std::function<int()>* text_join = nullptr,
-                 const DevWait* l2_wait = nullptr) {
+                 const DevWait* l2_wait = nullptr, unsigned* start_sig = nullptr) {
   const dcue_model* m = c.m;
   if (c.text && !t->tokens) return DCUE_ERR_INVALID;
   const int src = t->dtype == 0 ? SRC_TRACK_F16 : SRC_TRACK_F32;
@@ -545,6 +556,7 @@ int item_forward(const Ctx& c, const Ws& w, const dcue_tracks* t, const int32_t*
     a.M = M;
     a.nout = l == 5 ? c.D : c.H;
     if (l == 2 && l2_wait) a.wait = *l2_wait;  // (plans: the previous step's late Adam, on the device)
+    if (l == 1) a.start_sig = start_sig;  // (plans: the step's start, for the side streams)
     if (l == 2 && train) {  // conv 2's input-gradient operands, left by the split plans' late Adam
       a.rp = pack_seg(m, c.poff, 2);
       a.rp.fwd = a.rp.f16 = -1;
@@ -629,7 +641,7 @@ int user_forward(const Ctx& c, const Ws& w, const int64_t* users, int B, float* 
 // the same, with the deferred rows' sync in one launch (k_user_fwd): the train forward's user tower;
 // sig: the plan's signal word its workgroups add to once uf is stored (DevWait)
 int user_forward_fused(const Ctx& c, const Ws& w, const int64_t* users, int B, hipStream_t s,
-                       unsigned* sig = nullptr) {
+                       unsigned* sig = nullptr, DevWait start = DevWait{}) {
   const dcue_model* m = c.m;
   TGemmArgs g1 = {}, g2 = {};
   g1.M = B; g1.N = c.E; g1.K = c.E;
@@ -642,7 +654,7 @@ int user_forward_fused(const Ctx& c, const Ws& w, const int64_t* users, int B, h
   g2.B = c.P(SEG_L2_W); g2.sbk = 1; g2.sbn = c.E;
   g2.bias = c.P(SEG_L2_B);
   g2.C = w.uf; g2.scm = c.D; g2.scn = 1;
-  return launch_user_fwd(m, g1, g2, users, B, s, sig);
+  return launch_user_fwd(m, g1, g2, users, B, s, sig, start);
 }
 
 // whether a gather batch gets per-item copy lists (the prologue's histogram path)
@@ -858,7 +870,10 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   hipStream_t su = sp->st[0];
   // the user tower runs beside the item tower; the item tower's chain is issued first
   hipEvent_t ev_in = o.ev_in;
-  if (!ev_in) TRY(fork_point(sp, s, &ev_in));
+  // plans in the steady state: conv 1 -- the first kernel of the step on `s` -- raises the start signal
+  // and the side streams' first kernels wait for it on the device; no event is recorded
+  const bool start_dev = o.start_wait.flag != nullptr && !capturing_step();
+  if (!ev_in && !start_dev) TRY(fork_point(sp, s, &ev_in));
   HPROF("capi:3");
   if (!o.prologue_done) TRY(batch_counts(b, w, s));
   HPROF("capi:4");
@@ -878,7 +893,10 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   // the user tower on su: emb rows brought up to date, then the two GEMMs (+ the text branch, the
   // rolling flush slice)
   const std::function<int()> user_part = [&]() -> int {
-    TRY(wait_point(su, ev_in));
+    // the step's start: k_user_fwd's own wait (the three-launch form: a relay ahead of it), or ev_in
+    const DevWait ustart = start_dev && !split_fwd ? o.start_wait : DevWait{};
+    if (start_dev && split_fwd) TRY(launch_wait_signals(&o.start_wait, 1, su));
+    if (!start_dev) TRY(wait_point(su, ev_in));
     HPROF("capi:5");
     TRY(debug_delay(DCUE_SITE_USER_FWD, su));
     // The rows' sync and the two GEMMs in one launch (k_user_fwd); DCUE_USER_FWD=split issues them
@@ -889,7 +907,7 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
     TimerScope tsu;  // (the fused launch is timed live: DCUE_TIMED_USER_FWD)
     TRY(timer_begin(&tsu, split_fwd ? -1 : DCUE_TIMED_USER_FWD, su));
     if (tsu.b && !tsu.capturing) {  // a timed launch: the timer's stop event is its end
-      TRY(user_forward_fused(c, w, b->users, b->n_rows, su, ufs));
+      TRY(user_forward_fused(c, w, b->users, b->n_rows, su, ufs, ustart));
       ev_uf = tsu.b;
       TRY(timer_end(&tsu));
     } else {  // (untimed, or a captured plan: its timer node follows the launch)
@@ -898,7 +916,7 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
         if (m->emb_step) TRY(launch_emb_sync(m, b->users, b->n_rows, su));
         TRY(user_forward(c, w, b->users, b->n_rows, nullptr, su));
       } else {
-        TRY(user_forward_fused(c, w, b->users, b->n_rows, su, ufs));
+        TRY(user_forward_fused(c, w, b->users, b->n_rows, su, ufs, ustart));
       }
       HPROF("capi:7");
       TRY(fk.done());
@@ -913,8 +931,14 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
       // point (the items) and the previous step's late Adam (its weights); the previous step's text
       // weight gradient, which read xfc / tidx, ran on this same stream
       hipStream_t stx = sp->st[2];
-      TRY(wait_point(stx, ev_in));
-      if (o.wait_late) TRY(wait_point(stx, o.wait_late));
+      if (start_dev) {  // a relay: the start signal and, where the plan signals it, the late Adam
+        const DevWait tw[2] = {o.start_wait, o.late_wait};
+        TRY(launch_wait_signals(tw, 2, stx));
+        if (o.wait_late && !o.late_wait.flag) TRY(wait_point(stx, o.wait_late));
+      } else {
+        TRY(wait_point(stx, ev_in));
+        if (o.wait_late) TRY(wait_point(stx, o.wait_late));
+      }
       // the position-merge tickets: cleared by the step prologue (plans, before ev_in), else here --
       // item_forward's clear on the caller's stream leaves them out
       if (!(train && o.prologue_done) && w.ntick)
@@ -963,7 +987,14 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   // with the side-issue thread (side.hip) the user tower is issued there, beside the item tower's issue
   SideQueue side;
   int ust = DCUE_OK;
-  const uint64_t useq = side.threaded() ? side.run(user_part, &ust) : 0;
+  // (a part that waits for the start signal is enqueued only after conv 1, which raises it, has been)
+  uint64_t useq = 0;
+  const bool post_after_l1 = start_dev && side.threaded();
+  const std::function<int()> post_user = [&]() -> int {
+    useq = side.run(user_part, &ust);
+    return ust;
+  };
+  if (side.threaded() && !post_after_l1) TRY(post_user());
   // (under an exchange the late Adam follows the all-reduce: it keeps its wait before conv 2)
   const bool late_first = o.wait_late && late_wait_at_conv1() && !o.comm;
   if (late_first) TRY(wait_point(s, o.wait_late));
@@ -980,8 +1011,9 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   TRY(item_forward(c, w, t, b->item_track, b->n_items, copies, train != 0, w.counts, nullptr, s,
                    o.prologue_done, o.input_stats_done && o.prologue_done, o.clear_bn0,
                    late_first || l2_dev ? nullptr : o.wait_late,
-                   early && !side.threaded() ? &user_part : nullptr, o.sync_bn,
-                   text_side ? &text_join : nullptr, l2_dev ? &o.late_wait : nullptr));
+                   post_after_l1 ? &post_user : early && !side.threaded() ? &user_part : nullptr, o.sync_bn,
+                   text_side ? &text_join : nullptr, l2_dev ? &o.late_wait : nullptr,
+                   start_dev ? const_cast<unsigned*>(o.start_wait.flag) : nullptr));
   if (!early && !side.threaded() && !user_done) TRY(user_part());
   TRY(side.wait(useq));
   if (!uf_sig) TRY(wait_point(s, ev_uf));
@@ -1068,6 +1100,15 @@ bool late_wait_at_conv1() {
   static const bool on = [] {
     const char* e = getenv("DCUE_LATE_WAIT");
     return e && e[0] == 'c' && e[4] == '1';
+  }();
+  return on;
+}
+
+// DCUE_LATE_JOIN=hop: split plans keep the join through wgrad stream 0 (A/B, backward_impl)
+static bool late_join_hop() {
+  static const bool on = [] {
+    const char* e = getenv("DCUE_LATE_JOIN");
+    return e && e[0] == 'h';
   }();
   return on;
 }
@@ -1161,10 +1202,46 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   }
   if (c.text && !t->tokens) return DCUE_ERR_INVALID;
   hipEvent_t tail[4] = {};  // caller's stream, user stream, wgrad streams 0 and 1
+  // Plans (round 7, DCUE_XQ_FORK): the backward's fork points on the device. dgrad 4 and dgrad 3 signal
+  // from their own workgroups (RowsArgs::done_sig) instead of carrying a launch-bound event -- which
+  // cost the chain a gap before its next kernel -- and each side stream's consumer follows a one-wave
+  // relay (k_wait_signals) instead of a cross-queue event wait. fork_wait[l]: what the consumers of g_l
+  // wait for (flag null: ev_layer[l]). Not with the A/B orders that hand ev_layer[3] on
+  // (DCUE_AHEAD_AT=fork, DCUE_FORK_ONCE, DCUE_SCORE_FORK) or SyncBN, which keep the events.
+  const bool fork_dev = o.sig && o.sig_issued && xq_edge_on(XQ_FORK) && !capturing_step() && !o.ahead &&
+                        !fork_once() && !o.sync_bn && !(o.score_done && *o.score_done) && !o.item_only;
+  DevWait fork_wait[6] = {};
+  // (DCUE_XQ_LATE) the late Adam's joins the same way: each weight-gradient stream's reduce is followed
+  // by k_signal, and a relay ahead of the late Adam on the user stream waits for both words
+  const bool late_dev = o.sig && o.sig_issued && xq_edge_on(XQ_LATE) && !capturing_step() && o.dense_split &&
+                        !o.comm && !late_join_hop();
+  DevWait late_join[2] = {};  // wgrad streams 0 and 1
+  // DCUE_LATE_SIG_WG=1 (A/B): the reduces' workgroups signal themselves (WgradMulti::done_sig) instead
+  // of a k_signal launch behind each reduce -- 513 and about 1,000 agent-scope releases a step
+  static const bool late_sig_wg = [] {
+    const char* e = getenv("DCUE_LATE_SIG_WG");
+    return e && e[0] == '1';
+  }();
+  int late_blocks[2] = {1, 1};  // what each stream's launch adds to its word
+  if (late_dev) {
+    if (late_sig_wg) {
+      late_blocks[1] = wgrad_reduce_blocks(H, H, layer_geom(2).ks);
+      late_blocks[0] = wgrad_reduce_blocks(D, H, layer_geom(5).ks);
+      for (int l = 3; l <= 4; ++l) late_blocks[0] += wgrad_reduce_blocks(H, H, layer_geom(l).ks);
+      if (!c.res && !c.text) late_blocks[0] += wgrad_reduce_blocks(D, D, 1);  // (the fc slot)
+    }
+    late_join[0] = DevWait{o.sig + kSigWgradHi, o.sig_issued[kSigWgradHi] += (unsigned)late_blocks[0],
+                           user_fwd_fail_flag()};
+    late_join[1] = DevWait{o.sig + kSigWgrad2, o.sig_issued[kSigWgrad2] += (unsigned)late_blocks[1],
+                           user_fwd_fail_flag()};
+  }
   // user tower (userembedding.py:33-44 backward), the compact embedding rows, and -- when the step
   // carries it -- the user table's Adam step (it needs nothing from the item tower)
   auto user_bwd = [&]() -> int {
-    TRY(wait_point(su, ev_score ? ev_score : ev_layer[3]));
+    if (ev_score || !fork_wait[3].flag)
+      TRY(wait_point(su, ev_score ? ev_score : ev_layer[3]));
+    else  // (a relay: the first k_tgemm2 follows it in stream order)
+      TRY(launch_wait_signals(&fork_wait[3], 1, su));
     HPROF("capi:26");
     TRY(debug_delay(DCUE_SITE_USER_BWD, su));
     {
@@ -1257,7 +1334,11 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // xhat0 and the fc weight gradient) once dgrad 3 is (beside dgrad 2 and the conv-1 tail); each
   // + one reduce launch.
   auto issue_multi = [&](int lo, int hi, bool with_fc, hipStream_t so, hipEvent_t after, hipEvent_t* tl) -> int {
-    TRY(wait_point(so, after));
+    const DevWait& after_dev = fork_wait[lo];
+    if (after_dev.flag)
+      TRY(launch_wait_signals(&after_dev, 1, so));
+    else
+      TRY(wait_point(so, after));
     TRY(debug_delay(lo == 2 ? DCUE_SITE_WGRAD_2 : DCUE_SITE_WGRAD_HI, so));
     WgradMulti mw = {};
     if (with_fc) {  // fc: dW[n][k] = sum_m df[m][n] bn5(y5)[m][k], db = sum_m df (df final since item_grad)
@@ -1300,7 +1381,15 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
       mw.dW[j] = c.Gd(seg_conv_w(l));
       mw.db[j] = c.Gd(seg_conv_b(l));
     }
-    {
+    if (late_dev) {  // the late Adam's relay waits for this stream's word (no event bound)
+      const int slot = lo == 2 ? kSigWgrad2 : kSigWgradHi;
+      if (late_sig_wg) {
+        mw.done_sig = o.sig + slot;
+        mw.done_blocks = late_blocks[lo == 2];
+      }
+      TRY(launch_conv_wgrad_multi(mw, so));
+      if (!late_sig_wg) TRY(launch_signal(o.sig + slot, late_join[lo == 2].val, so));
+    } else {
       ForkAfter fk(sp, so, tl);
       TRY(launch_conv_wgrad_multi(mw, so));
       TRY(fk.done());
@@ -1319,10 +1408,7 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // cross-queue wait on a pending event costs the waiting queue ≈4 µs, measured; on the side
   // stream that time is slack, on the caller's it is the step's). DCUE_LATE_JOIN=hop keeps the join
   // in split plans too, for the A/B.
-  static const bool hop = [] {
-    const char* e = getenv("DCUE_LATE_JOIN");
-    return e && e[0] == 'h';
-  }();
+  const bool hop = late_join_hop();
   // split plans without an exchange: the late Adam on the user stream waits for the prepared inputs
   // and the next launch waits for it before conv 1 (late_wait_at_conv1)
   const bool inputs_via_late = o.dense_split && !o.comm && o.late_done && late_wait_at_conv1();
@@ -1357,6 +1443,8 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
     if (o.dense_split) {
       if (hop) {
         TRY(wait_point(su, joined));
+      } else if (late_dev) {
+        TRY(launch_wait_signals(late_join, 2, su));
       } else {
         TRY(wait_point(su, tail[2]));
         TRY(wait_point(su, tail[3]));
@@ -1469,7 +1557,24 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
     const RowsArgs ra = dgrad_args(l);
     // a fork point only where a side stream waits (wgrads of layers 3-5 after g_3, of layer 2
     // after g_2): every event bound to a launch costs the chain a gap before its next kernel
-    if ((l - 1 == 3 && !fork_once()) || l - 1 == 2) {
+    if (fork_dev && (l - 1 == 3 || l - 1 == 2)) {
+      // the fork point as a signal: the launch's workgroups count into the word, nothing is bound
+      const int slot = l - 1 == 3 ? kSigDgrad4 : kSigDgrad3;
+      RowsArgs rs = ra;
+      rs.done_sig = o.sig + slot;
+      fork_wait[l - 1] = DevWait{o.sig + slot, o.sig_issued[slot] += (unsigned)conv_dgrad_blocks(l, H, H, M),
+                                 user_fwd_fail_flag()};
+      TRY(debug_delay(l - 1 == 3 ? DCUE_SITE_DGRAD_4 : DCUE_SITE_DGRAD_3, s));
+      TRY(launch_conv_dgrad(l, H, rs, s));
+      // (the consumers' relays are enqueued after this launch: posted here, FIFO on the side thread)
+      if (l - 1 == 3) {
+        if (thr) TRY(post(multi_hi));
+        TRY(after_fork3());
+      } else if (thr) {
+        TRY(post(multi_2));
+      }
+    } else if ((l - 1 == 3 && !fork_once()) || l - 1 == 2) {
+      TRY(debug_delay(l - 1 == 3 ? DCUE_SITE_DGRAD_4 : DCUE_SITE_DGRAD_3, s));
       ForkAfter fk(sp, s, &ev_layer[l - 1]);
       TRY(launch_conv_dgrad(l, l == 5 ? D : H, ra, s));
       if (sync) {  // the weight gradients forked here read the summed BN_{l-1} sums: the fork point
@@ -1492,6 +1597,7 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
       }
     } else {
       if (l == 2) TRY(debug_delay(DCUE_SITE_DGRAD_2, s));
+      if (l == 4) TRY(debug_delay(DCUE_SITE_DGRAD_4, s));  // (DCUE_FORK_ONCE: no fork point after it)
       TRY(launch_conv_dgrad(l, l == 5 ? D : H, ra, s));
       if (sync) TRY(comm_allreduce_u64(o.sync_bn, bn_acc(w.bnbacc, w.cmax, l - 1), 4L * w.cmax, s));
     }
@@ -1570,12 +1676,15 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   };
   // layer 1 (the step's tail) follows the chain on the caller's stream, issued right away
   if (ev_x0) TRY(wait_point(s, ev_x0));
-  if (o.wait_inputs && !inputs_via_late && !inputs_dev) {
+  if (o.wait_inputs && !inputs_via_late) {
+    // the host's wait holds for the device-side wait too: the kernel that polls is enqueued only
+    // after the side thread has enqueued the launch that signals (enqueue order)
     TRY(side.wait(o.ahead ? ahead_seq : o.wait_inputs_seq));
-    TRY(wait_point(s, o.wait_inputs));
+    if (!inputs_dev) TRY(wait_point(s, o.wait_inputs));
   }
   TRY(debug_delay(DCUE_SITE_WGRAD_1, s));
-  TRY(issue_wgrad(1, s, 2, &tail[0]));
+  // (split plans without an exchange: nothing waits for the caller stream's tail -- no event bound)
+  TRY(issue_wgrad(1, s, 2, o.dense_split && !o.comm ? nullptr : &tail[0]));
   HPROF("capi:22");
 
   if (!thr) {

@@ -69,6 +69,14 @@ void conv_dgrad_shape(int layer, int kc, int nout, int M, int32_t* out) {
   rows_shape(M, gm.lin, choose_tw(rows, max_tw(gm.lin, gm.ks, kc)), nout, dgrad_f16(true, rows), out);
 }
 
+// run_rows' grid for that launch: the row tiles at choose_tw's width times the 128-column blocks
+long conv_dgrad_blocks(int layer, int kc, int nout, int M) {
+  const LayerGeom gm = layer_geom(layer);
+  const long total = (long)M * gm.lin;
+  const long rows = 16L * choose_tw(total, max_tw(gm.lin, gm.ks, kc));
+  return ((total + rows - 1) / rows) * ((nout + 127) / 128);
+}
+
 int launch_conv_dgrad(int layer, int kc, const RowsArgs& a, hipStream_t s) {
   switch (layer) {
     case 2: return dgrad_kc<2>(kc, a, s);

@@ -55,6 +55,15 @@ void conv_fwd_shape(int layer, int kc, int nout, int M, int32_t* out) {
   rows_shape(M, R, choose_tw((long)M * R, max_tw(R, gm.ks, kc)), nout, fwd_f16(true), out);
 }
 
+// run_rows' grid for that launch (as conv_dgrad_blocks)
+long conv_fwd_blocks(int layer, int kc, int nout, int M) {
+  const LayerGeom gm = layer_geom(layer);
+  const int R = gm.lp * gm.pool;
+  const long total = (long)M * R;
+  const long rows = 16L * choose_tw(total, max_tw(R, gm.ks, kc));
+  return ((total + rows - 1) / rows) * ((nout + 127) / 128);
+}
+
 int launch_conv_fwd(int layer, int kc, int src, const RowsArgs& a, hipStream_t s) {
   switch (layer) {
     case 1: return fwd_kc<1>(kc, src, a, s);

@@ -299,6 +299,12 @@ __device__ __forceinline__ void conv_rows_body(const RowsArgs& a, const int bx, 
   [[maybe_unused]] constexpr int KID = 2 + MODE * 5 + (LIN >= 131 ? 0 : LIN >= 32 ? 1 : LIN >= 8 ? 2 : LIN >= 2 ? 3 : 4);
   DCUE_KTW(KID, 6);
   DCUE_KT(KID, 0);
+  // (plans: the step's first kernel on the caller's stream tells the side streams that the stream
+  // has reached the step -- RowsArgs::start_sig)
+  if (MODE == 0 && a.start_sig && bx == 0 && by == 0 && threadIdx.x == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __hip_atomic_fetch_add(a.start_sig, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
   const ChanPre cpre = chan_preload<SRC, F16>(a, KC);
   // (plans, conv 2: the previous step's late Adam on the user stream wrote its weights -- read below,
   // after the loads above, which read only this stream's data)
@@ -449,7 +455,10 @@ __device__ __forceinline__ void conv_rows_body(const RowsArgs& a, const int bx, 
   DCUE_KT(KID, 1);
   __syncthreads();
   DCUE_KT(KID, 2);
-  if (!colok) return;  // no barrier follows
+  if (!colok) {  // no barrier follows, but for the one of dev_signal_wg at the end (dgrad, plans)
+    if (MODE == 1 && a.done_sig) __syncthreads();
+    return;
+  }
 
   int sbase[TW];
 #pragma unroll
@@ -653,6 +662,8 @@ __device__ __forceinline__ void conv_rows_body(const RowsArgs& a, const int bx, 
       }
     }
   }
+  // (plans: the weight gradients and the user tower's backward on the side streams wait for this)
+  if constexpr (MODE == 1) dev_signal_wg(a.done_sig);
   DCUE_KT(KID, 4);
   DCUE_KTW(KID, 7);
 }

@@ -2154,6 +2154,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_multi(WgradMulti w) {
   const WgradArgs& a = w.a[j];
   wgrad_reduce_body(a.wpart, a.bpart, w.nchunk[j], a.cout, a.cin, layer_geom(w.layer[j] == 6 ? 5 : w.layer[j]).ks, 1,
                     w.dW[j], w.db[j], nullptr, nullptr, b - w.rstart[j]);
+  dev_signal_wg(w.done_sig);  // (plans, A/B: the late Adam's relay waits for every workgroup)
 }
 
 int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
@@ -2175,7 +2176,8 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
   if (w.layer[0] == 2 && wgrad_kernel(2, w.a[0].cin, w.a[0].cout, SRC_ACT, w.n == 1) == WK_16T) {  // layer 2 alone
     const WgradArgs& a = w.a[0];
     TRY((wgrad16t_launch<2, SRC_ACT>(a, w.nchunk[0], s)));
-    w.rstart[1] = (int)(((long)a.cout * 4 * a.cin + 127) / 128 + (a.cout + 127) / 128);
+    w.rstart[1] = wgrad_reduce_blocks(a.cout, a.cin, 4);
+    if (w.done_sig && w.rstart[1] != w.done_blocks) return DCUE_ERR_INVALID;
     DCUE_LAUNCH(k_wgrad_reduce_multi, dim3((unsigned)w.rstart[1]), dim3(256), 0, s, w);
     DCUE_LAUNCH_CHECK();
     return DCUE_OK;
@@ -2191,8 +2193,9 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
     w.kt[j] = (gm.ks * a.cin + 127) / 128;
     w.ot[j] = (a.cout + 127) / 128;
     w.start[j + 1] = w.start[j] + w.kt[j] * w.ot[j] * w.nchunk[j];
-    w.rstart[j + 1] = w.rstart[j] + (int)(((long)a.cout * gm.ks * a.cin + 127) / 128 + (a.cout + 127) / 128);
+    w.rstart[j + 1] = w.rstart[j] + wgrad_reduce_blocks(a.cout, a.cin, gm.ks);
   }
+  if (w.done_sig && w.rstart[w.n] != w.done_blocks) return DCUE_ERR_INVALID;
   if (f16)
   {
     // two workgroups per CU (the layer-5 / fc branch spills 148 B per lane at that register budget);

@@ -199,6 +199,10 @@ __device__ __forceinline__ float ord_value(unsigned k) {
 // barrier packet of 5-10 us even when its event completed long before; this costs one L2 round trip
 // when the producer is done. Values grow by one per issue (wrap-safe compare). A wait that gives up
 // (never expected: the producer is issued right after) sets bit 1 of the device fail word.
+// Round 7 runs the other direction too: producers on the caller's stream (the step's first kernel,
+// dgrad 4, dgrad 3) signal from inside the kernel, and a side stream's consumer either waits inside
+// its own kernel (k_user_fwd, k_step_prologue) or follows a one-wave relay, k_wait_signals, in
+// stream order (tail.hip). Every kernel that polls is enqueued after the launch that signals.
 struct DevWait {
   const unsigned* flag;  // null: no wait
   unsigned val;

@@ -126,6 +126,12 @@ struct RowsArgs {
   float* rp_wpack;  // the model's wpack
   PackSeg rp;
   DevWait wait;  // plans: a side stream's signal to wait for at the kernel's start (conv 2: the late Adam)
+  // plans (DevWait). start_sig (forward, the step's first kernel on the caller's
+  // stream): workgroup (0, 0) adds 1 at its entry -- everything enqueued on the stream before the
+  // launch has completed by then. done_sig (dgrad): every workgroup adds 1 once its stores are done
+  // (dev_signal_wg; the host adds conv_dgrad_blocks to the word's issue counter)
+  unsigned* start_sig;
+  unsigned* done_sig;
 };
 
 struct WgradArgs {
@@ -174,7 +180,16 @@ struct WgradMulti {
   int kt[kWgradMultiMax], ot[kWgradMultiMax];  // kc / o tiles per layer
   int start[kWgradMultiMax + 1];      // wgrad block ranges
   int rstart[kWgradMultiMax + 1];     // reduce block ranges
+  // plans (DCUE_LATE_SIG_WG=1, A/B): every workgroup of the reduce adds 1 once its sums are stored
+  // (dev_signal_wg); done_blocks: the reduce's grid as the host counted it into the word's issue
+  // counter (wgrad_reduce_blocks per slot) -- a launch whose grid differs is refused
+  unsigned* done_sig;
+  int done_blocks;
 };
+// workgroups of one slot's part of k_wgrad_reduce_multi (ks: the layer's taps; the fc slot: 1)
+inline int wgrad_reduce_blocks(int cout, int cin, int ks) {
+  return (int)(((long)cout * ks * cin + 127) / 128 + (cout + 127) / 128);
+}
 int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s);
 // the weight-gradient kernels (conv_wgrad.hip wgrad_kernel; dcue_debug_launch_shape reports the number)
 enum {
@@ -198,6 +213,9 @@ bool wgrad_f16_on();
 
 int launch_conv_fwd(int layer, int kc, int src, const RowsArgs& a, hipStream_t s);
 int launch_conv_dgrad(int layer, int kc, const RowsArgs& a, hipStream_t s);
+// workgroups of that launch over M items (each adds 1 to RowsArgs::done_sig)
+long conv_dgrad_blocks(int layer, int kc, int nout, int M);
+long conv_fwd_blocks(int layer, int kc, int nout, int M);
 int launch_conv_wgrad(int layer, int src, const WgradArgs& a, int nchunk, hipStream_t s);
 // xhat0[i][t + 2][c] = (x[track_i][t][c] - mean0[c]) * invstd0[c] in a [M][kXp][128] zero-padded
 // layout, bn0's batch statistics finalized from its accumulators (layer 1's wgrad reads it from `xsrc`)
@@ -351,6 +369,9 @@ struct StepPrologue {
   // drew the item in (row, j) order
   int32_t* copy_ptr;
   int32_t* copy_idx;
+  // plans: signals to wait for before anything else (the step's start on the caller's stream, the
+  // previous step's late Adam) in place of stream waits ahead of the launch; flag null: none
+  DevWait wait[2];
 };
 int launch_step_prologue(const StepPrologue& p, hipStream_t s);
 
@@ -377,7 +398,7 @@ int launch_tgemm(int ta, int tb, const TGemmArgs& g, hipStream_t s);
 // the user tower's forward in one launch (adam.hip k_user_fwd): deferred mode's row sync, then g1
 // (h1 = relu(E[users]) W1^T + b1) and g2 (uf = relu(h1) W2^T + b2) as launch_tgemm(1, 0, .) computes them
 int launch_user_fwd(const dcue_model* md, const TGemmArgs& g1, const TGemmArgs& g2, const int64_t* users, int B,
-                    hipStream_t s, unsigned* sig = nullptr);
+                    hipStream_t s, unsigned* sig = nullptr, DevWait start = DevWait{});
 int user_fwd_blocks(int B);  // k_user_fwd's workgroups (each adds 1 to sig)
 // two independent GEMMs in one launch: g1 as launch_tgemm(0, 1, .) with a k-strided A, g2 as
 // launch_tgemm(0, 0, .) with a k-contiguous A; both with n-contiguous B (the user tower's backward)
@@ -393,8 +414,25 @@ int launch_score_fused(const float* uf, const float* f, const dcue_batch* b, int
                        float* dfcopy, hipStream_t s, DevWait uf_wait = DevWait{});
 // k_signal: store `val` into the signal word `flag` once the stream's earlier work is done (DevWait)
 int launch_signal(unsigned* flag, unsigned val, hipStream_t s);
-// a plan's signal words (StepOpts::sig): the user tower's output, the late Adam, the prepared inputs
-enum SigSlot { kSigUf = 0, kSigLate = 1, kSigInputs = 2, kSigText = 3, kSigSlots = 16 };
+// k_wait_signals: a one-wave relay on a side stream -- one lane polls up to three signal words (as
+// dev_wait: bounded, bit 1 of the fail word when it gives up) and exits; the next kernel on `s`
+// follows in stream order, and its start-of-kernel acquire sees the producers' data. w[i].flag null:
+// skipped.
+constexpr int kWaitSignalsMax = 3;
+int launch_wait_signals(const DevWait* w, int n, hipStream_t s);
+// a plan's signal words (StepOpts::sig): the user tower's output, the late Adam, the prepared inputs;
+// round 7: the step's start on the caller's stream, the input gradients of conv 4 and conv 3 (the
+// backward's fork points), the ends of the two weight-gradient streams' launches (the late Adam's joins)
+enum SigSlot {
+  kSigUf = 0, kSigLate = 1, kSigInputs = 2, kSigText = 3, kSigStart = 4, kSigDgrad4 = 5, kSigDgrad3 = 6,
+  kSigWgradHi = 7, kSigWgrad2 = 8, kSigSlots = 16
+};
+// The A/B knobs of round 7's device-side edges, each on unless set to 0: DCUE_XQ_START (the step's
+// start: user tower, prologue, text branch), DCUE_XQ_FORK (dgrad 4 / dgrad 3 -> weight gradients and
+// the user tower's backward), DCUE_XQ_LATE (weight-gradient tails -> late Adam). DCUE_XQ_WAIT=event
+// turns every device-side wait off (plan.hip dev_waits_on).
+enum XqGroup { XQ_START = 0, XQ_FORK = 1, XQ_LATE = 2 };
+bool xq_edge_on(int group);
 int launch_score_bwd(const float* uf, const float* f, const dcue_batch* b, int d,
                      const float* dscores, const float* cosv, const float* norms, float* du,
                      float* dfcopy, hipStream_t s);
@@ -538,6 +576,7 @@ bool& capturing_step();
 // the scope's ring event is bound to each launch (LaunchTag; the last binding is what a wait sees).
 // If the scope launched nothing, or the step is being captured, done() records the event instead.
 // Scopes nest: launches of an inner scope do not bind the outer event, so the outer one records.
+// ev == nullptr: a point nobody waits for -- the scope binds and records nothing.
 class ForkAfter {
  public:
   ForkAfter(SidePool* p, hipStream_t s, hipEvent_t* ev);
@@ -630,7 +669,8 @@ struct StepOpts {
   const dcue_adam_args* emb_adam = nullptr;  // backward: also step the user table (parts = EMBEDDING)
   hipEvent_t* score_done = nullptr;     // forward (fuse_score): a fork point after the score kernel
   // backward: where the step ends, for a caller that prepares the next one (plans): [0] the
-  // caller's stream after its last kernel, [1] wgrad stream 0 once every side stream's part is in
+  // caller's stream after its last kernel (null on split steps without an exchange: nothing waits
+  // for it, so no event is bound there), [1] wgrad stream 0 once every side stream's part is in
   hipEvent_t* tails = nullptr;
   // prepared ahead (plans): the step's copy counts and its cleared accumulator block, in place of
   // the workspace's own
@@ -667,6 +707,10 @@ struct StepOpts {
   DevWait late_wait{};
   DevWait* late_sig = nullptr;
   DevWait inputs_wait{};
+  // round 7: the step's start, raised by the forward's first kernel on the caller's stream (conv 1:
+  // the plan sets it only where conv 1 is that kernel) -- the user tower and the text branch wait for
+  // it on the device instead of for ev_in, which is then null and not recorded
+  DevWait start_wait{};
   // the step's per-item copy lists (gather layout, built by the plan's prologue; StepPrologue)
   const int32_t* copy_ptr = nullptr;
   const int32_t* copy_idx = nullptr;

@@ -137,12 +137,6 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
     TRY(fork_point(sp, s, &p->tails[0]));
     HPROF("plan:2");
   }
-  // A point on the caller's stream at this launch's start: the user tower, this launch's prologue
-  // for the next step and the lookahead wait for it (it orders them after everything the caller
-  // enqueued before the launch -- the batch indices, the announced next items -- and after the last
-  // step, which ended on this stream).
-  hipEvent_t ev_in = nullptr;
-  TRY(fork_point(sp, s, &ev_in));
   dcue_batch b = b0;
   if (users_src) b.users = users_src;
   if (items_src) b.item_track = items_src;
@@ -151,6 +145,37 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   const bool prepared = p->ahead_items[cur] != nullptr;
   const bool ahead = prepared && items_src == p->ahead_items[cur];
   p->ahead_items[cur] = nullptr;
+  // DCUE_PROLOGUE_FIRST=1: the prologue closure is posted before the forward (A/B)
+  static const bool prologue_first = [] {
+    const char* e = getenv("DCUE_PROLOGUE_FIRST");
+    return e && e[0] == '1';
+  }();
+  // device-side waits (no communicator: its exchange keeps the event orders)
+  const bool dev = p->sig && !p->comm && dev_waits_on();
+  // A point on the caller's stream at this launch's start (ev_in): the user tower, this launch's
+  // prologue for the next step and the lookahead wait for it (it orders them after everything the
+  // caller enqueued before the launch -- the batch indices, the announced next items -- and after the
+  // last step, which ended on this stream).
+  // In the steady state that point is a signal instead (round 7, DCUE_XQ_START): a step whose inputs
+  // were prepared ahead starts with conv 1 on the caller's stream, and that kernel's first workgroup
+  // adds 1 to the plan's start word at its entry -- when everything enqueued before it has completed,
+  // which is what an event recorded here would say. The user tower and the prologue wait for the
+  // word inside their kernels, the text branch behind a relay; no event is recorded. The first
+  // launch, steps that start with another kernel (no lookahead: k_input_stats) and the prologue-first
+  // order keep the event. So do steps whose conv 1 needs every CU (catalogue plans): the kernels that
+  // poll are resident before conv 1 starts -- k_user_fwd's workgroups and the 1024-thread prologue,
+  // one CU each -- and a conv-1 grid of more workgroups than the CUs they leave then runs its last
+  // round short of them: the catalogue step (M = 1,344) measured 0.497 ms with the signal against
+  // 0.470-0.475 with the event, which those kernels reach only once conv 1 holds its CUs.
+  constexpr long kCUs = 256;  // MI355X
+  const bool conv1_leaves_cus = conv_fwd_blocks(1, kMels, st_hidden(&p->model.dims), b0.n_items) +
+                                    user_fwd_blocks(b0.n_rows) + 1 <= kCUs;
+  const bool start_dev =
+      dev && xq_edge_on(XQ_START) && p->launches > 0 && ahead && !prologue_first && conv1_leaves_cus;
+  DevWait start_wait{};
+  if (start_dev) start_wait = DevWait{p->sig + kSigStart, ++p->sig_issued[kSigStart], user_fwd_fail_flag()};
+  hipEvent_t ev_in = nullptr;
+  if (!start_dev) TRY(fork_point(sp, s, &ev_in));
   // The next step's inputs (slot nxt) are made on wgrad stream 0, which split plans never join back
   // into the caller's stream: the prologue (draws, copy counts, cleared accumulators, published
   // batch) and the lookahead (the announced next batch's bn0 sums and, on the f32 path, its xhat0),
@@ -175,8 +200,6 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   p->next_items = nullptr;
   p->inputs_ready = ring_event(sp);  // slot nxt's inputs, for the next launch (recorded below)
   // the lookahead, then the inputs_ready record, on wgrad stream 0 after `after`
-  // device-side waits (no communicator: its exchange keeps the event orders)
-  const bool dev = p->sig && !p->comm && dev_waits_on();
   DevWait in_sig{};
   if (dev && inputs_wait == 1) in_sig = DevWait{p->sig + kSigInputs, ++p->sig_issued[kSigInputs], user_fwd_fail_flag()};
   const std::function<int(hipEvent_t)> lookahead = [p, sa, nxt, look, ir = p->inputs_ready, in_sig](hipEvent_t after) -> int {
@@ -220,6 +243,7 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
     o.late_wait = p->late_sig;
     o.late_sig = &late_sig;
     o.inputs_wait = in_sig;
+    o.start_wait = start_wait;
   }
   // the previous step's rolling-flush slice runs after this step's user tower (StepOpts)
   const bool deferred = p->model.emb_step != nullptr;
@@ -235,11 +259,6 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   }();
   hipEvent_t score_done = nullptr;
   if (score_fork) o.score_done = &score_done;
-  // DCUE_PROLOGUE_FIRST=1: the prologue closure is posted before the forward (A/B)
-  static const bool prologue_first = [] {
-    const char* e = getenv("DCUE_PROLOGUE_FIRST");
-    return e && e[0] == '1';
-  }();
   auto post_prologue = [&]() -> int {
     StepPrologue q = inputs(nxt);
     if (inbatch) {
@@ -258,9 +277,18 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
     // waits for) orders the prologue after all of them. Without this wait a delayed layer-2 weight
     // gradient read a cleared range -- a NaN operand scale -- and the step's conv-2 gradient went
     // non-finite (tests/test_gpu_races.py).
-    const hipEvent_t prev_late = legacy_orders() ? nullptr : p->late_done;
+    // (steady state, start_dev: both orders inside the prologue kernel -- the start word and the
+    // late Adam's signal word, the value the previous launch issued into it)
+    hipEvent_t prev_late = legacy_orders() ? nullptr : p->late_done;
+    if (start_dev) {
+      q.wait[0] = start_wait;
+      if (prev_late && p->late_sig.flag) {
+        q.wait[1] = p->late_sig;
+        prev_late = nullptr;
+      }
+    }
     iseq = side.run([q, sa, ev_in, prev_late, &lookahead]() -> int {
-      TRY(wait_point(sa, ev_in));
+      if (ev_in) TRY(wait_point(sa, ev_in));
       if (prev_late) TRY(wait_point(sa, prev_late));
       TRY(debug_delay(DCUE_SITE_PROLOGUE, sa));
       TRY(launch_step_prologue(q, sa));

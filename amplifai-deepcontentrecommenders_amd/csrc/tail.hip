@@ -408,6 +408,29 @@ int launch_signal(unsigned* flag, unsigned val, hipStream_t s) {
   return DCUE_OK;
 }
 
+// DevWait's consumer side as a relay (dcue_internal.h launch_wait_signals): one wave that holds no
+// LDS, one lane polling, so it can sit on a side stream for as long as the producer takes
+struct WaitSignals {
+  DevWait w[kWaitSignalsMax];
+};
+__global__ __launch_bounds__(64) void k_wait_signals(WaitSignals a) {
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int i = 0; i < kWaitSignalsMax; ++i) dev_wait_order(a.w[i]);
+}
+
+int launch_wait_signals(const DevWait* w, int n, hipStream_t s) {
+  if (n < 0 || n > kWaitSignalsMax) return DCUE_ERR_INVALID;
+  WaitSignals a = {};
+  int k = 0;
+  for (int i = 0; i < n; ++i)
+    if (w[i].flag) a.w[k++] = w[i];
+  if (!k) return DCUE_OK;
+  DCUE_LAUNCH(k_wait_signals, dim3(1), dim3(64), 0, s, a);
+  DCUE_LAUNCH_CHECK();
+  return DCUE_OK;
+}
+
 // k_score_fused's CPW by the copies per row, 1 + n_neg (0: the general instantiation)
 static int score_cpw(int n_neg) { return n_neg + 1 <= 16 ? 4 : n_neg + 1 <= 32 ? 8 : 0; }
 

@@ -127,7 +127,7 @@ TOPK_METRIC_NAMES = ("precision", "recall", "ndcg", "map", "mrr", "hit")  # DCUE
 TOPK_FLAG_NO_TRUTH, TOPK_FLAG_BAD_INDEX = 1, 2
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
-               "conv2", "dgrad_2", "wgrad_1", "text_fwd")
+               "conv2", "dgrad_2", "wgrad_1", "text_fwd", "dgrad_4", "dgrad_3")
 
 _P = ctypes.c_void_p
 _SIGS = {

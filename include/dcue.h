@@ -425,7 +425,10 @@ int dcue_plan_destroy(dcue_plan* plan);
 #define DCUE_SITE_DGRAD_2 9    /* caller's stream: conv-2 input gradient (g1) */
 #define DCUE_SITE_WGRAD_1 10   /* caller's stream: conv-1 weight gradient */
 #define DCUE_SITE_TEXT_FWD 11  /* text tower: the text branch's forward on its side stream (ABI 16) */
-#define DCUE_N_DEBUG_SITES 12
+/* (added under ABI 17: appended, nothing earlier changes) the backward's two fork points */
+#define DCUE_SITE_DGRAD_4 12   /* caller's stream: conv-4 input gradient (g3) */
+#define DCUE_SITE_DGRAD_3 13   /* caller's stream: conv-3 input gradient (g2) */
+#define DCUE_N_DEBUG_SITES 14
 int dcue_debug_delay(int32_t site, int32_t microseconds);
 /* Probes: buf = NULL (off) or a device array of dcue_debug_probe_count() records
  * { uint32 nonfinite; uint32 nonzero; uint64 first_bad } (the caller sets first_bad to UINT64_MAX
