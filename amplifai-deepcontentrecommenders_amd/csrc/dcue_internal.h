@@ -624,6 +624,15 @@ bool late_wait_at_conv1();
 __host__ __device__ constexpr int rank_dp(int d) { return (d + 15) & ~15; }
 // k_rank_normalize: y[r] = x[rows ? rows[r] : r] / max(||.||, 1e-8), zero-padded to dp
 int launch_rank_normalize(const float* x, const int32_t* rows, int64_t n, int d, int dp, float* y, hipStream_t s);
+// k_rank_pad: y[r] = x[rows ? rows[r] : r], zero-padded to dp, unscaled (DCUE_SCORE_DOT)
+int launch_rank_pad(const float* x, const int32_t* rows, int64_t n, int d, int dp, float* y, hipStream_t s);
+
+// ------------------------------------------------------------- WRMF Gram (wrmf.hip, wrmf_objective.hip)
+// G = F^T F in fp64 for F [n][dim] fp32 (n >= 1, dim <= 128): the chunk partials into `part`
+// ([wrmf_gram_chunks(n)][dim][dim]) and their fixed-order sum into G ([D16][D16], D16 = dim rounded
+// up to 16, zero past dim)
+long wrmf_gram_chunks(long n_fixed);
+int launch_wrmf_gram(const float* F, long n, int dim, double* part, double* G, hipStream_t s);
 
 // ---------------------------------------------------------------- diagnostics (debug.hip)
 // a spin kernel ahead of the work at `site` when a delay is set for it (dcue_debug_delay)

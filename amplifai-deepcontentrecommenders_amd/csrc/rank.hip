@@ -50,6 +50,25 @@ int launch_rank_normalize(const float* x, const int32_t* rows, int64_t n, int d,
   return DCUE_OK;
 }
 
+// one wave per row: y = x, zero padding to DP (rows[] may gather) -- the prep pass of the inner-product
+// score (dcue_topk_scored, DCUE_SCORE_DOT): k_rank_normalize without the norm
+__global__ __launch_bounds__(256) void k_rank_pad(const float* __restrict__ x, const int32_t* rows, int64_t n,
+                                                  int d, int dp, float* __restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const int64_t src = rows ? (int64_t)rows[r] : r;
+  const float* xr = x + src * d;
+  float* yr = y + r * dp;
+  for (int k = lane; k < dp; k += 64) yr[k] = k < d ? xr[k] : 0.f;
+}
+
+int launch_rank_pad(const float* x, const int32_t* rows, int64_t n, int d, int dp, float* y, hipStream_t s) {
+  DCUE_LAUNCH(k_rank_pad, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, x, rows, n, d, dp, y);
+  DCUE_LAUNCH_CHECK();
+  return DCUE_OK;
+}
+
 // S[q][c] for q < nq, c < nc. Wave w owns candidate columns 16w..16w+15 of the tile and all four
 // 16-query row tiles; k is split across the four lane groups (g = lane>>4 covers k = g*DP/4 + j), so
 // every lane reads DP/4 consecutive floats of its row.

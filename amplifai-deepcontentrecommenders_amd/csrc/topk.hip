@@ -4,7 +4,9 @@
 // written: the scores of a 64-candidate tile live in the MFMA accumulators and only the few that
 // beat the query's current K-th best leave them.
 //
-//   k_rank_normalize  (rank.hip) x / max(||x||, 1e-8), zero-padded to DP, both sides
+//   k_rank_normalize  (rank.hip) x / max(||x||, 1e-8), zero-padded to DP, both sides; under
+//                     DCUE_SCORE_DOT (dcue_topk_scored) k_rank_pad instead: the raw rows, zero-padded
+//                     -- the score is then the inner product, and everything below is unchanged
 //   k_topk_scores     grid (query tiles, candidate splits). The workgroup keeps its query tile in LDS
 //                     and streams its candidate chunk through one LDS slab (the next tile's global
 //                     loads are in flight during the MFMA loop). Scores as k_rank_scores computes
@@ -417,11 +419,14 @@ int dcue_topk_workspace_bytes(int64_t n_cand, int32_t d, int32_t query_batch, in
   return DCUE_OK;
 }
 
-int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_feat, int64_t n_cand, int32_t d,
-              const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr, const int32_t* excl_idx,
-              const uint8_t* cand_mask, int32_t k, int32_t query_batch, int32_t cand_split, void* ws,
-              size_t ws_bytes, int32_t* out_idx, float* out_score, int32_t* out_count, int32_t* out_flags,
-              void* stream) {
+int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                     int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
+                     const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k, int32_t query_batch,
+                     int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
+                     int32_t* out_count, int32_t* out_flags, void* stream) {
+  if (score != DCUE_SCORE_COSINE && score != DCUE_SCORE_DOT) return DCUE_ERR_INVALID;
+  // the prep pass of both sides: unit rows (cosine) or the raw rows (inner product), zero-padded to dp
+  const auto prep = score == DCUE_SCORE_DOT ? launch_rank_pad : launch_rank_normalize;
   if (!query_feat || !cand_feat || !queries || !ws || !out_idx || !out_score || !out_count || !out_flags ||
       n_query_rows <= 0 || n_queries < 0 || (excl_ptr == nullptr) != (excl_idx == nullptr))
     return DCUE_ERR_INVALID;
@@ -452,12 +457,12 @@ int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_f
   // zero rows past the last candidate / query of a tile: the kernels load whole tiles
   const int64_t cand_pad = (int64_t)n_tiles * 64 - n_cand;
   if (cand_pad) DCUE_HIP_CHECK(hipMemsetAsync(w.cn + (size_t)n_cand * dp, 0, (size_t)cand_pad * dp * sizeof(float), s));
-  TRY(launch_rank_normalize(cand_feat, nullptr, n_cand, d, dp, w.cn, s));
+  TRY(prep(cand_feat, nullptr, n_cand, d, dp, w.cn, s));
   for (int32_t q0 = 0; q0 < n_queries; q0 += qb) {
     const int nq = n_queries - q0 < qb ? n_queries - q0 : qb;
     const int q_pad = (nq + 63) / 64 * 64 - nq;
     if (q_pad) DCUE_HIP_CHECK(hipMemsetAsync(w.qn + (size_t)nq * dp, 0, (size_t)q_pad * dp * sizeof(float), s));
-    TRY(launch_rank_normalize(query_feat, queries + q0, nq, d, dp, w.qn, s));
+    TRY(prep(query_feat, queries + q0, nq, d, dp, w.qn, s));
     TopkArgs a;
     a.qn = w.qn;
     a.nq = nq;
@@ -487,6 +492,16 @@ int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_f
   }
   DCUE_HIP_CHECK(hipStreamSynchronize(s));
   return DCUE_OK;
+}
+
+int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_feat, int64_t n_cand, int32_t d,
+              const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr, const int32_t* excl_idx,
+              const uint8_t* cand_mask, int32_t k, int32_t query_batch, int32_t cand_split, void* ws,
+              size_t ws_bytes, int32_t* out_idx, float* out_score, int32_t* out_count, int32_t* out_flags,
+              void* stream) {
+  return dcue_topk_scored(DCUE_SCORE_COSINE, query_feat, n_query_rows, cand_feat, n_cand, d, queries, n_queries,
+                          excl_ptr, excl_idx, cand_mask, k, query_batch, cand_split, ws, ws_bytes, out_idx,
+                          out_score, out_count, out_flags, stream);
 }
 
 }  // extern "C"

@@ -1074,6 +1074,24 @@ long wrmf_gram_chunks(long n_fixed) {
   return c < kWrmfGramMaxBlocks ? c : kWrmfGramMaxBlocks;
 }
 
+// G = F^T F: the chunk partials, then their fixed-order sum (shared with wrmf_objective.hip)
+int launch_wrmf_gram(const float* F, long n, int dim, double* part, double* G, hipStream_t s) {
+  const long nch = wrmf_gram_chunks(n);
+  static const bool scalar_gram = [] {  // DCUE_WRMF_GRAM=scalar: k_wrmf_gram (fp64 FMAs), A/B and check
+    const char* e = getenv("DCUE_WRMF_GRAM");
+    return e && e[0] == 's';
+  }();
+  if (scalar_gram)
+    DCUE_LAUNCH(k_wrmf_gram, dim3((unsigned)nch), dim3(256), 0, s, F, n, dim, part);
+  else
+    DCUE_LAUNCH(k_wrmf_gram_mfma, dim3((unsigned)nch), dim3(256), 0, s, F, n, dim, part);
+  DCUE_LAUNCH_CHECK();
+  const long dd = (long)((dim + 15) & ~15) * ((dim + 15) & ~15);
+  DCUE_LAUNCH(k_wrmf_gram_reduce, dim3((unsigned)((dd + 255) / 256)), dim3(256), 0, s, part, (int)nch, dim, G);
+  DCUE_LAUNCH_CHECK();
+  return DCUE_OK;
+}
+
 }  // namespace dcue
 
 extern "C" {
@@ -1103,18 +1121,7 @@ int dcue_wrmf_half_step(float* solve, int64_t n_rows, const float* fixed, int64_
   const long nch = wrmf_gram_chunks(n_fixed);
   wacc_t* part = reinterpret_cast<wacc_t*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
   wacc_t* G = part + (size_t)nch * dim * dim;
-  static const bool scalar_gram = [] {  // DCUE_WRMF_GRAM=scalar: k_wrmf_gram (fp64 FMAs), A/B and check
-    const char* e = getenv("DCUE_WRMF_GRAM");
-    return e && e[0] == 's';
-  }();
-  if (scalar_gram)
-    DCUE_LAUNCH(k_wrmf_gram, dim3((unsigned)nch), dim3(256), 0, s, fixed, (long)n_fixed, (int)dim, part);
-  else
-    DCUE_LAUNCH(k_wrmf_gram_mfma, dim3((unsigned)nch), dim3(256), 0, s, fixed, (long)n_fixed, (int)dim, part);
-  DCUE_LAUNCH_CHECK();
-  const long dd = (long)((dim + 15) & ~15) * ((dim + 15) & ~15);
-  DCUE_LAUNCH(k_wrmf_gram_reduce, dim3((unsigned)((dd + 255) / 256)), dim3(256), 0, s, part, (int)nch, (int)dim, G);
-  DCUE_LAUNCH_CHECK();
+  TRY(launch_wrmf_gram(fixed, (long)n_fixed, (int)dim, part, G, s));
   if (n_rows == 0) return DCUE_OK;
   const size_t lds = wrmf_solve_lds_bytes();
   // the dynamic-LDS limit is a per-device function attribute: set it on every call (cheap), so a

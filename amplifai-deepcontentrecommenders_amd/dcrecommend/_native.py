@@ -120,6 +120,8 @@ COMM_F32, COMM_U64 = 0, 1  # dcue_host_allreduce_fn dtypes
 HOST_ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32)
 RANK_SPLIT, RANK_SINGLE = 0, 1
 TOPK_MAX_K = 128  # DCUE_TOPK_MAX_K
+SCORE_COSINE, SCORE_DOT = 0, 1  # dcue_topk_scored (added under ABI 17): DCUE_SCORE_*
+SCORES = {"cosine": SCORE_COSINE, "dot": SCORE_DOT}
 # dcue_topk_metrics (added under ABI 17): cutoffs per call, metrics per cutoff and their slots, flag bits
 TOPK_METRICS_MAX_CUTOFFS = 8
 TOPK_N_METRICS = 6
@@ -205,6 +207,13 @@ _SIGS = {
     "dcue_topk": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32, _P, _P, _P,
                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P],
                   ctypes.c_int),
+    "dcue_topk_scored": ([ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                          _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P,
+                          _P, _P], ctypes.c_int),
+    "dcue_wrmf_objective_workspace_bytes": ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                             ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_wrmf_objective": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
+                             ctypes.c_double, _P, ctypes.c_size_t, _P, _P], ctypes.c_int),
     "dcue_topk_metrics": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, ctypes.c_int64, _P,
                            ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "dcue_topk_metrics_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P, _P, _P],

@@ -97,3 +97,53 @@ class DCBR:
             return out[:, :self.feature_dim]
         finally:
             self.net.train()
+
+    # ------------------------------------------------------------------ serving
+    @torch.no_grad()
+    def item_factors(self, tracks, items=None, batch=1344):
+        """Predicted factors [n, feature_dim] (device) of the tracks `items` (track ids; default every
+        track of `tracks`): predict() in chunks of `batch` into one tensor. The net is left in train
+        mode, as predict leaves it."""
+        nat.require_gpu(tracks, "tracks")
+        if items is None:
+            items = torch.arange(tracks.shape[0], device=tracks.device)
+        items = torch.as_tensor(items).to(tracks.device).reshape(-1)
+        if int(batch) < 1:
+            raise ValueError("batch must be positive")
+        out = torch.empty((items.shape[0], self.feature_dim), dtype=torch.float32, device=tracks.device)
+        for a in range(0, items.shape[0], int(batch)):
+            out[a:a + int(batch)] = self.predict(tracks, items[a:a + int(batch)])
+        return out
+
+    @staticmethod
+    def _cold_items(wrmf, cold):
+        """The cold item rows as an int64 device tensor: `cold`, or the items without a by_item pair."""
+        if cold is None:
+            indptr = wrmf.by_item[0]
+            return torch.nonzero(indptr[1:] == indptr[:-1]).reshape(-1)
+        return torch.as_tensor(cold, dtype=torch.int64).to(wrmf.device).reshape(-1)
+
+    def hybrid_item_factors(self, wrmf, tracks, cold=None):
+        """A copy of wrmf.item_factors with the rows of `cold` replaced by the ConvNet's predicted
+        factors -- the cold-start table of van den Oord et al.: songs without usage are ranked by what
+        their audio predicts. Item row i is track i of `tracks`. cold: item rows (default: the items
+        whose by_item row is empty)."""
+        if self.feature_dim != wrmf.factors:
+            raise ValueError("the ConvNet predicts %d factors, the WRMF model has %d" % (self.feature_dim, wrmf.factors))
+        table = wrmf.item_factors.clone()
+        cold = self._cold_items(wrmf, cold)
+        if cold.numel():
+            if int(cold.min()) < 0 or int(cold.max()) >= table.shape[0]:
+                raise ValueError("cold item rows must lie in [0, %d)" % table.shape[0])
+            table[cold] = self.item_factors(tracks, cold)
+        return table
+
+    def recommend(self, wrmf, users, k, tracks, cold=None, cold_only=False, exclude_seen=True):
+        """wrmf.recommend over the hybrid table (hybrid_item_factors); cold_only restricts the
+        candidates to the cold rows ("new releases for this user")."""
+        table = self.hybrid_item_factors(wrmf, tracks, cold)
+        mask = None
+        if cold_only:
+            mask = torch.zeros(table.shape[0], dtype=torch.uint8, device=table.device)
+            mask[self._cold_items(wrmf, cold)] = 1
+        return wrmf.recommend(users, k, exclude_seen=exclude_seen, item_factors=table, cand_mask=mask)

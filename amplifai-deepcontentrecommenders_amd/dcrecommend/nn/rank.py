@@ -73,7 +73,10 @@ def mean_until_missing(values, has_pos):
 
 def _upload_csr(ptr, idx, device):
     """(int64 pointers, int32 indices) on the device; an empty index array becomes one unused entry,
-    so that its address is never null."""
+    so that its address is never null. Tensors (a CSR already on a device) are taken as they are."""
+    if torch.is_tensor(ptr):
+        idx = idx if idx.numel() else torch.zeros(1, dtype=torch.int32)
+        return ptr.to(device, torch.int64).contiguous(), idx.to(device, torch.int32).contiguous()
     idx = np.ascontiguousarray(idx, dtype=np.int32)
     return (torch.from_numpy(np.ascontiguousarray(ptr, dtype=np.int64)).to(device),
             torch.from_numpy(idx if len(idx) else np.zeros(1, np.int32)).to(device))
@@ -102,6 +105,18 @@ def _nonfinite_error(queries, bad):
     non-finite factors make NaN scores)."""
     return ValueError("Input contains NaN. (DCUE scores of query %d: the model's factors are not "
                       "finite)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+
+
+def _nonfinite_dot_error(queries, bad):
+    """The same for inner-product scores, which finite factors can overflow."""
+    return ValueError("Input contains NaN or infinity. (inner-product scores of query %d: the factors are not "
+                      "finite or the product overflowed)" % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+
+
+def _score_mode(score):
+    if score not in nat.SCORES:
+        raise ValueError("score must be one of %s, got %r" % (sorted(nat.SCORES), score))
+    return nat.SCORES[score]
 
 
 class _Workspace:
@@ -181,12 +196,14 @@ class TopK(_Workspace):
 
     excl_ptr [n_query_rows + 1] int64 / excl_idx int32: per query row, the sorted candidates never to
     return (both None: no exclusion); cand_mask [n_cand] uint8 (None: every candidate; then n_cand
-    must be given)."""
+    must be given). score: "cosine" (nn.CosineSimilarity, dcue_topk) or "dot" (the inner product of the
+    raw rows, dcue_topk_scored: what WRMF factors are ranked by)."""
 
     DEFAULT_QUERY_BATCH = 4096
 
-    def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None):
+    def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None, score="cosine"):
         self.device = torch.device(device)
+        self.score = _score_mode(score)
         if (excl_ptr is None) != (excl_idx is None):
             raise ValueError("excl_ptr and excl_idx go together")
         self.excl_ptr = self.excl_idx = None
@@ -196,6 +213,9 @@ class TopK(_Workspace):
 
     def workspace_bytes(self, d, qb, k, cand_split=0):
         return self._nbytes("dcue_topk_workspace_bytes", self.n_cand, d, qb, k, cand_split)
+
+    def _nonfinite(self, queries, bad):
+        return (_nonfinite_error if self.score == nat.SCORE_COSINE else _nonfinite_dot_error)(queries, bad)
 
     def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
         """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
@@ -220,11 +240,14 @@ class TopK(_Workspace):
             d = int(query_feat.shape[1])
             qb = int(min(nq, self.DEFAULT_QUERY_BATCH if query_batch is None else query_batch))
             ws = self._grow(self.workspace_bytes(d, qb, k, int(cand_split)))
-            nat.check(nat.lib().dcue_topk(
-                nat.ptr(query_feat), query_feat.shape[0], nat.ptr(cand_feat), self.n_cand, d, nat.ptr(q), nq,
-                nat.ptr(self.excl_ptr), nat.ptr(self.excl_idx), nat.ptr(self.cand_mask), k, qb, int(cand_split),
-                nat.ptr(ws), ws.numel(), nat.ptr(idx), nat.ptr(score), nat.ptr(count), nat.ptr(flags),
-                nat.stream_handle(self.device)), "dcue_topk")
+            args = (nat.ptr(query_feat), query_feat.shape[0], nat.ptr(cand_feat), self.n_cand, d, nat.ptr(q), nq,
+                    nat.ptr(self.excl_ptr), nat.ptr(self.excl_idx), nat.ptr(self.cand_mask), k, qb, int(cand_split),
+                    nat.ptr(ws), ws.numel(), nat.ptr(idx), nat.ptr(score), nat.ptr(count), nat.ptr(flags),
+                    nat.stream_handle(self.device))
+            if self.score == nat.SCORE_COSINE:
+                nat.check(nat.lib().dcue_topk(*args), "dcue_topk")
+            else:
+                nat.check(nat.lib().dcue_topk_scored(self.score, *args), "dcue_topk_scored")
         return idx[:nq], score[:nq], count[:nq], flags[:nq]
 
     def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
@@ -232,12 +255,13 @@ class TopK(_Workspace):
         with fewer than k eligible candidates end in idx -1 / score -inf.
 
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
-        infinite: a diverged model fails here as it fails in DCUE.score."""
+        infinite: a diverged model fails here as it fails in DCUE.score (score="dot": the factors are
+        not finite or the product overflowed)."""
         idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split)
         flags = flags.cpu().numpy()
         bad = (flags & 2).astype(bool)
         if bad.any():
-            raise _nonfinite_error(queries, bad)
+            raise self._nonfinite(queries, bad)
         return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
 
 
@@ -259,12 +283,13 @@ class TopKMetrics(_Workspace):
     dcue_topk_metrics / dcue_topk_metrics_mean): no list is copied to the host, no score matrix exists.
 
     truth_ptr [n_query_rows + 1] int64 / truth_idx int32: per query row, the sorted held-out candidates
-    (dcue_topk's exclusion format); excl_ptr / excl_idx, cand_mask, n_cand: as TopK, which it owns for
-    the lists."""
+    (dcue_topk's exclusion format); excl_ptr / excl_idx, cand_mask, n_cand, score: as TopK, which it owns
+    for the lists."""
 
-    def __init__(self, truth_ptr, truth_idx, device, excl_ptr=None, excl_idx=None, cand_mask=None, n_cand=None):
+    def __init__(self, truth_ptr, truth_idx, device, excl_ptr=None, excl_idx=None, cand_mask=None, n_cand=None,
+                 score="cosine"):
         self.device = torch.device(device)
-        self.topk = TopK(excl_ptr, excl_idx, cand_mask, self.device, n_cand=n_cand)
+        self.topk = TopK(excl_ptr, excl_idx, cand_mask, self.device, n_cand=n_cand, score=score)
         self.cand_mask, self.n_cand = self.topk.cand_mask, self.topk.n_cand
         truth_ptr = np.ascontiguousarray(truth_ptr, dtype=np.int64)
         truth_idx = np.ascontiguousarray(truth_idx, dtype=np.int32)
@@ -363,7 +388,7 @@ class TopKMetrics(_Workspace):
             nonfinite[q0:q0 + len(part)] = tflags
         bad = (nonfinite[:n].cpu().numpy() & 2).astype(bool)
         if bad.any():
-            raise _nonfinite_error(queries, bad)
+            raise self.topk._nonfinite(queries, bad)
         mean, cov, n_eval = self.mean_raw(out[:n], flags[:n], exposure)
         mean = mean.cpu().numpy()
         res = {"ks": list(ks), "n_evaluated": int(n_eval.cpu().numpy()[0])}

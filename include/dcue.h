@@ -611,6 +611,51 @@ int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_f
               const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k, int32_t query_batch,
               int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
               int32_t* out_count, int32_t* out_flags, void* stream);
+/* (added under ABI 17) dcue_topk with the score chosen by the caller -- every other argument, the
+ * workspace (dcue_topk_workspace_bytes) and every rule above unchanged:
+ *   DCUE_SCORE_COSINE: dcue_topk itself (dcue_topk is this call with that value; same bits).
+ *   DCUE_SCORE_DOT: the plain inner product of the raw rows, q . c -- what a matrix factorisation
+ *     (WRMF: x_u . y_i) ranks by, where the row norms carry the popularity the cosine divides out.
+ *     The two prep passes gather and zero-pad the rows without scaling them; the score kernel, the
+ *     keys, the selection, eligibility, the tie order, the padding of short lists and out_count are
+ *     dcue_topk's, and so is the summation order (it depends on d alone): the lists do not depend on
+ *     query_batch or cand_split, bit for bit. out_flags bit 1 keeps its meaning; a dot product of
+ *     large finite factors can overflow where a cosine cannot, and then sets it too. +-inf order as
+ *     ordinary values, a NaN is never returned.
+ * Any other `score` is DCUE_ERR_INVALID, on the host before the first device call. */
+#define DCUE_SCORE_COSINE 0
+#define DCUE_SCORE_DOT 1
+int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                     int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries,
+                     const int64_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k,
+                     int32_t query_batch, int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx,
+                     float* out_score, int32_t* out_count, int32_t* out_flags, void* stream);
+
+/* ------------------------------------------------------------ WRMF objective (added under ABI 17) */
+/* The objective the ALS half-steps (dcue_wrmf_half_step) descend,
+ *   L = sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2),
+ * over ALL n_users x n_items pairs (p = 1, c = 1 + alpha v on the observed ones; p = 0, c = 1
+ * elsewhere) without the dense matrix: with s_ui = x_u . y_i,
+ *   L = sum_{(u,i) observed} [c_ui (1 - s_ui)^2 - s_ui^2]  +  sum_{a,b} (X^T X)_ab (Y^T Y)_ab
+ *       +  lambda (tr X^T X + tr Y^T Y)
+ * (the middle term is sum_{u,i} s_ui^2 over every pair). Everything in fp64, accumulated from the
+ * fp32 factors: the first two terms cancel to a few percent of their size near a fit.
+ *   X [n_users][dim], Y [n_items][dim] fp32, dim <= 128; indptr[n_users+1] / indices / values: the
+ *     by-user CSR in dcue_wrmf_half_step's format (values null: v = 1). A pair listed twice counts
+ *     twice. An index outside [0, n_items) is not dereferenced; it makes the observed term NaN.
+ *   out (device) [4] doubles: L, the observed term, the all-pairs term, the regulariser.
+ * Every reduction has a fixed order -- a pair's dot product a fixed cross-lane tree, a row's pairs in
+ * pair order, the rows a tree whose shape depends on n_users alone, the Grams dcue_wrmf_half_step's
+ * -- so two calls give the same bits. Validated on the host before the first device call
+ * (DCUE_ERR_INVALID: a null X / Y / indptr / out / ws, indices null with n_users > 0, n_users < 0,
+ * n_items < 0, dim outside 1..128, lambda <= 0; DCUE_ERR_WORKSPACE). n_users == 0, n_items == 0 or a
+ * CSR without pairs is DCUE_OK: the observed term is 0 and the other two are what the factors give.
+ * alpha and lambda are doubles here (dcue_wrmf_half_step rounds its own to fp32: a relative 6e-8 of
+ * lambda, which moves its minimiser, and so L, only in second order). Asynchronous on `stream`. Workspace: the Gram partials, both Grams and one double per user. */
+int dcue_wrmf_objective_workspace_bytes(int64_t n_users, int64_t n_items, int32_t dim, size_t* bytes_host);
+int dcue_wrmf_objective(const float* X, int64_t n_users, const float* Y, int64_t n_items, int32_t dim,
+                        const int64_t* indptr, const int32_t* indices, const float* values, double alpha,
+                        double lambda, void* ws, size_t ws_bytes, double* out, void* stream);
 
 /* ------------------------------------------------------ fold-in of unseen users (added under ABI 17) */
 /* A user outside the trained table -- a new listener, a playlist, a session -- gets a factor without
