@@ -18,15 +18,17 @@
 //                         floating-point atomics would make the sum depend on arrival order): thread
 //                         (g, column) sums the rows g, g + G, g + 2G, ... of its column in that order,
 //                         G = 1024 / 6m row groups; a column's G partials are then added in ascending
-//                         g. The order depends on n_queries and m only. Then coverage: one pass over
+//                         g (colmean.h col_means, shared with k_list_ild_mean). The order depends on
+//                         n_queries and m only. Then coverage: one pass over
 //                         the candidates, integer counts of those whose exposure up to cutoff i is
 //                         non-zero and of the mask's non-zero bytes.
 #include "dcue_internal.h"
+#include "colmean.h"
 
 namespace dcue {
 
 constexpr int kTmPos = DCUE_TOPK_MAX_K;  // list positions: two per lane
-constexpr int kTmMeanThreads = 1024;
+constexpr int kTmMeanThreads = kColMeanThreads;
 static_assert(kTmPos == 128, "k_topk_metrics gives each lane of a wave64 two list positions");
 static_assert(6 * DCUE_TOPK_METRICS_MAX_CUTOFFS <= 64, "one lane per output of a query");
 
@@ -179,12 +181,6 @@ __global__ __launch_bounds__(256) void k_topk_metrics(const int32_t* __restrict_
   }
 }
 
-__device__ __forceinline__ int tm_wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kTmMeanThreads) void k_topk_metrics_mean(
     const double* __restrict__ metrics, const int32_t* __restrict__ flags, int nq, int m,
     const int32_t* __restrict__ exposure, const uint8_t* __restrict__ mask, int n_cand, double* __restrict__ out_mean,
@@ -192,37 +188,9 @@ __global__ __launch_bounds__(kTmMeanThreads) void k_topk_metrics_mean(
   __shared__ double part[kTmMeanThreads];
   __shared__ int cnt[2 + DCUE_TOPK_METRICS_MAX_CUTOFFS];  // evaluated, mask bytes set, covered[i]
   const int tid = threadIdx.x, lane = tid & 63;
-  const int m6 = 6 * m, G = kTmMeanThreads / m6;
   if (tid < 2 + DCUE_TOPK_METRICS_MAX_CUTOFFS) cnt[tid] = 0;
   __syncthreads();
-
-  double s = 0.0;
-  if (tid < G * m6) {
-    const int col = tid % m6;
-    int r = tid / m6;
-    for (; r + 3 * G < nq; r += 4 * G) {  // four rows' loads in flight, added in row order
-      const int f0 = flags[r], f1 = flags[r + G], f2 = flags[r + 2 * G], f3 = flags[r + 3 * G];
-      const double x0 = metrics[(size_t)r * m6 + col], x1 = metrics[(size_t)(r + G) * m6 + col];
-      const double x2 = metrics[(size_t)(r + 2 * G) * m6 + col], x3 = metrics[(size_t)(r + 3 * G) * m6 + col];
-      s += f0 ? 0.0 : x0;
-      s += f1 ? 0.0 : x1;
-      s += f2 ? 0.0 : x2;
-      s += f3 ? 0.0 : x3;
-    }
-    for (; r < nq; r += G) s += flags[r] ? 0.0 : metrics[(size_t)r * m6 + col];
-  }
-  part[tid] = s;
-  int ne = 0;
-  for (int r = tid; r < nq; r += kTmMeanThreads) ne += flags[r] == 0;
-  ne = tm_wave_sum_int(ne);
-  if (lane == 0 && ne) atomicAdd(&cnt[0], ne);
-  __syncthreads();
-  if (tid < m6) {
-    double tot = 0.0;
-    for (int g = 0; g < G; ++g) tot += part[g * m6 + tid];
-    out_mean[tid] = cnt[0] > 0 ? tot / (double)cnt[0] : 0.0;
-  }
-  if (tid == 0) *out_n = cnt[0];
+  col_means(metrics, flags, nq, 6 * m, part, &cnt[0], out_mean, out_n);
   if (!exposure) return;  // (uniform)
 
   int cov[DCUE_TOPK_METRICS_MAX_CUTOFFS], set = 0;
@@ -238,12 +206,12 @@ __global__ __launch_bounds__(kTmMeanThreads) void k_topk_metrics_mean(
         cov[i] += seen;
       }
   }
-  set = tm_wave_sum_int(set);
+  set = wave_sum_int(set);
   if (lane == 0 && set) atomicAdd(&cnt[1], set);
 #pragma unroll
   for (int i = 0; i < DCUE_TOPK_METRICS_MAX_CUTOFFS; ++i)
     if (i < m) {
-      const int v = tm_wave_sum_int(cov[i]);
+      const int v = wave_sum_int(cov[i]);
       if (lane == 0 && v) atomicAdd(&cnt[2 + i], v);
     }
   __syncthreads();

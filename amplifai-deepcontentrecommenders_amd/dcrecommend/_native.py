@@ -127,6 +127,10 @@ TOPK_METRICS_MAX_CUTOFFS = 8
 TOPK_N_METRICS = 6
 TOPK_METRIC_NAMES = ("precision", "recall", "ndcg", "map", "mrr", "hit")  # DCUE_TOPK_METRIC_* order
 TOPK_FLAG_NO_TRUTH, TOPK_FLAG_BAD_INDEX = 1, 2
+# dcue_list_mmr / dcue_list_ild (added under ABI 17): DCUE_MMR_REL_*, DCUE_LIST_FLAG_*
+MMR_REL_RAW, MMR_REL_MINMAX = 0, 1
+MMR_RELS = {"raw": MMR_REL_RAW, "minmax": MMR_REL_MINMAX}
+LIST_FLAG_NO_PAIR, LIST_FLAG_BAD_INDEX, LIST_FLAG_NONFINITE = 1, 2, 4
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd", "dgrad_4", "dgrad_3")
@@ -218,6 +222,13 @@ _SIGS = {
                            ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "dcue_topk_metrics_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, _P, _P, _P],
                                ctypes.c_int),
+    "dcue_list_mmr_workspace_bytes": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_list_mmr": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, ctypes.c_float,
+                       ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_list_ild": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                       _P, ctypes.c_size_t, _P, _P, _P], ctypes.c_int),
+    "dcue_list_ild_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),

@@ -206,17 +206,25 @@ class WRMF:
             self._serve[key] = rank.TopK(ptr, idx, None, self.device, n_cand=n_cand, score="dot")
         return self._serve[key]
 
-    def recommend(self, users, k=10, exclude_seen=True, item_factors=None, cand_mask=None):
+    def recommend(self, users, k=10, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
+                  pool=None):
         """The k best items for each user row by x_u . y_i: (idx int64 [n, k], score float32 [n, k],
         count int32 [n]) numpy arrays, best first, short lists padded with -1 / -inf. exclude_seen
         drops the items of the user's by_user row. item_factors [n_cand, factors] (device) replaces
         the candidate table (DCBR.hybrid_item_factors: predicted factors for cold items); cand_mask
-        [n_cand]: 0 = never return the item. One fused GPU pass (include/dcue.h dcue_topk_scored)."""
+        [n_cand]: 0 = never return the item. One fused GPU pass (include/dcue.h dcue_topk_scored).
+
+        diversity (lambda in [0, 1]; None: the plain ranking): the user's `pool` best items (default
+        min(128, 4 k)) re-ranked down to k by Maximal Marginal Relevance (dcue_list_mmr) -- the
+        inner-product scores min-max scaled per list, the redundancy the cosine of the candidate
+        factors, as similar_items measures it. The lists are then in selection order, each entry
+        with its own inner-product score."""
         cand = self._candidates(item_factors)
         if exclude_seen and cand.shape[0] != self.item_factors.shape[0]:
             raise ValueError("exclude_seen needs a candidate table with the fit's %d items" % self.item_factors.shape[0])
         tk = self._topk(exclude_seen, cand_mask, int(cand.shape[0]))
-        return tk.topk(self.user_factors, cand, np.asarray(users, dtype=np.int64).reshape(-1), k)
+        return tk.topk(self.user_factors, cand, np.asarray(users, dtype=np.int64).reshape(-1), k,
+                       diversity=diversity, pool=pool)
 
     def similar_items(self, items, k=10):
         """The k items most similar to each item row, by the cosine of the item factors (dcue_topk, as
@@ -268,23 +276,27 @@ class WRMF:
             torch.cuda.current_stream().synchronize()  # (indptr / indices / val are temporaries of this call)
         return out
 
-    def recommend_for(self, histories, k=10, exclude_history=True, values=None, item_factors=None, cand_mask=None):
+    def recommend_for(self, histories, k=10, exclude_history=True, values=None, item_factors=None, cand_mask=None,
+                      diversity=None, pool=None):
         """recommend() for users outside the fit: fold_in(histories, values), then the inner-product
-        top-k with each history as the user's exclusion row. Returns what recommend() returns."""
+        top-k with each history as the user's exclusion row. diversity / pool: as recommend(). Returns
+        what recommend() returns."""
         cand = self._candidates(item_factors)
         feat = self.fold_in(histories, values)
         ptr, idx = rank.histories_csr(histories) if exclude_history else (None, None)
         tk = rank.TopK(ptr, idx, self._mask(cand_mask), self.device, n_cand=int(cand.shape[0]), score="dot")
-        return tk.topk(feat, cand, np.arange(len(histories)), k)
+        return tk.topk(feat, cand, np.arange(len(histories)), k, diversity=diversity, pool=pool)
 
     def evaluate_topk(self, truth_ptr, truth_idx, ks=(10, 50, 100), users=None, exclude_ptr=None, exclude_idx=None,
-                      item_factors=None, cand_mask=None, per_user=False):
+                      item_factors=None, cand_mask=None, per_user=False, diversity=None, pool=None, ild=False):
         """Top-K ranking quality of the inner-product lists against held-out truth rows (a CSR over
         user rows, each row sorted, no repeats): DCUE.evaluate_topk's dict -- {"precision@K",
         "recall@K", "ndcg@K", "map@K", "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} --
         through rank.TopKMetrics(score="dot"). users: user rows (default: every row with truth);
         exclude_ptr / exclude_idx: what the lists must not return (the training interactions;
-        default none); per_user adds "users", "per_user" and "flags"."""
+        default none); per_user adds "users", "per_user" and "flags". diversity / pool: score
+        recommend(diversity=, pool=)'s MMR re-ranked lists (k = max(ks)) instead; ild adds "ild@K" (the
+        mean intra-list diversity of the scored lists, dcue_list_ild) and "n_ild"."""
         ks = rank.check_cutoffs(ks)
         cand = self._candidates(item_factors)
         ev = rank.TopKMetrics(truth_ptr, truth_idx, self.device, excl_ptr=exclude_ptr, excl_idx=exclude_idx,
@@ -293,11 +305,14 @@ class WRMF:
             rows = np.flatnonzero(np.diff(np.asarray(truth_ptr, dtype=np.int64)) > 0).astype(np.int64)
         else:
             rows = np.asarray(users, dtype=np.int64).reshape(-1)
-        res = ev.evaluate(self.user_factors, cand, rows, ks, per_query=per_user)
+        res = ev.evaluate(self.user_factors, cand, rows, ks, per_query=per_user, diversity=diversity, pool=pool,
+                          ild=ild)
         out = {"n_users": res["n_evaluated"]}
-        for name in nat.TOPK_METRIC_NAMES + ("coverage",):
+        for name in nat.TOPK_METRIC_NAMES + ("coverage",) + (("ild",) if ild else ()):
             for i, k in enumerate(ks):
                 out["%s@%d" % (name, k)] = float(res[name][i])
+        if ild:
+            out["n_ild"] = res["n_ild"]
         if per_user:
             out.update(users=rows.tolist(), per_user=res["per_query"], flags=res["flags"])
         return out

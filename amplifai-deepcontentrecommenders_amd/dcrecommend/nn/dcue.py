@@ -562,19 +562,25 @@ class DCUE(Trainer):
         return [[(names[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
                 for r in range(len(count))]
 
-    def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True):
+    def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None):
         """The k best songs for each user id, by the cosine of DCUE.score: one list per user of
         (song_id, score) pairs, best first (as_ids=False: the raw (idx [n, k], score [n, k],
         count [n]) arrays over item indices). Candidates are the dataset's (or loader's) split songs,
         or every song with audio; exclude_seen drops the songs the user interacted with in any
         split -- the "seen" set of the evaluator's negatives. One fused GPU pass
         (include/dcue.h dcue_topk) for all users; the reference has only predict(), one user and one
-        Python candidate list at a time. An unknown user id raises KeyError."""
+        Python candidate list at a time. An unknown user id raises KeyError.
+
+        diversity (lambda in [0, 1]; None: the plain ranking): the user's `pool` best songs (default
+        min(128, 4 k)) re-ranked down to k by Maximal Marginal Relevance over the item factors' cosine
+        (dcue_list_mmr): each pick maximises lambda * score - (1 - lambda) * (its largest similarity to
+        the songs picked before it). The lists are then in selection order, each with its own score."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         index = self._index_source(ds).user_index
         rows = np.array([index[u] for u in users], dtype=np.int64)
-        out = self._topk("user", ds, exclude_seen).topk(self.user_factors, self._item_feat_by_index(), rows, k)
+        out = self._topk("user", ds, exclude_seen).topk(self.user_factors, self._item_feat_by_index(), rows, k,
+                                                         diversity=diversity, pool=pool)
         return self._as_pairs(ds, *out) if as_ids else out
 
     def similar_songs(self, songs, k=10, dataset=None):
@@ -606,7 +612,8 @@ class DCUE(Trainer):
                                 np.flatnonzero(np.diff(ptr) > 0).astype(np.int64))
         return self._evals[key]
 
-    def evaluate_topk(self, dataset=None, ks=(10, 50, 100), users=None, per_user=False):
+    def evaluate_topk(self, dataset=None, ks=(10, 50, 100), users=None, per_user=False, diversity=None, pool=None,
+                      ild=False):
         """Top-K ranking quality of the current factors: {"precision@K", "recall@K", "ndcg@K", "map@K",
         "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} (include/dcue.h dcue_topk_metrics
         has the definitions). Candidates are the dataset's (or loader's) split songs with audio, or
@@ -617,7 +624,12 @@ class DCUE(Trainer):
         per_user adds "users" (the ids), "per_user" (numpy [n, len(ks), 6], slots in
         _native.TOPK_METRIC_NAMES order) and "flags" (bit 0: no truth). Every list is ranked and
         scored on the GPU (dcue_topk, then dcue_topk_metrics on its device output); the reference has
-        only DCUE.score's sampled AUC / mAP."""
+        only DCUE.score's sampled AUC / mAP.
+
+        diversity / pool: score recommend(diversity=, pool=)'s MMR re-ranked lists (k = max(ks)) instead.
+        ild adds "ild@K" -- the mean intra-list diversity (1 - cosine of the item factors, averaged
+        over the pairs of a list's first K songs; dcue_list_ild) of the lists that were scored -- and
+        "n_ild", the number of lists behind it."""
         ks = rank.check_cutoffs(ks)
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
@@ -629,11 +641,14 @@ class DCUE(Trainer):
         else:
             users = list(users)
             rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
-        res = ev.evaluate(self.user_factors, self._item_feat_by_index(), rows, ks, per_query=per_user)
+        res = ev.evaluate(self.user_factors, self._item_feat_by_index(), rows, ks, per_query=per_user,
+                          diversity=diversity, pool=pool, ild=ild)
         out = {"n_users": res["n_evaluated"]}
-        for name in nat.TOPK_METRIC_NAMES + ("coverage",):
+        for name in nat.TOPK_METRIC_NAMES + ("coverage",) + (("ild",) if ild else ()):
             for i, k in enumerate(ks):
                 out["%s@%d" % (name, k)] = float(res[name][i])
+        if ild:
+            out["n_ild"] = res["n_ild"]
         if per_user:
             out.update(users=users, per_user=res["per_query"], flags=res["flags"])
         return out
@@ -699,10 +714,11 @@ class DCUE(Trainer):
                              "finite)" % int(np.argmax(bad)))
         return emb, feat, loss
 
-    def recommend_for(self, histories, k=10, dataset=None, exclude_history=True, as_ids=True, **fold_in_kwargs):
+    def recommend_for(self, histories, k=10, dataset=None, exclude_history=True, as_ids=True, diversity=None,
+                      pool=None, **fold_in_kwargs):
         """recommend() for users outside the trained table: fold_in(histories, **fold_in_kwargs), then
         the fused top-k pass with each history as the user's exclusion list (every song of it, with
-        or without audio). Returns what recommend() returns."""
+        or without audio). diversity / pool: as recommend(). Returns what recommend() returns."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         usable, full = self._history_items(histories, ds)
@@ -714,7 +730,7 @@ class DCUE(Trainer):
         feat = self._fold_in(usable, ds, **args)[1]
         ptr, idx = rank.histories_csr(full) if exclude_history else (None, None)
         out = rank.TopK(ptr, idx, self._cand_mask(ds), self.device).topk(
-            feat, self._item_feat_by_index(), np.arange(len(full)), k)
+            feat, self._item_feat_by_index(), np.arange(len(full)), k, diversity=diversity, pool=pool)
         return self._as_pairs(ds, *out) if as_ids else out
 
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):

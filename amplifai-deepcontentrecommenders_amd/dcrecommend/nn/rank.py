@@ -12,6 +12,9 @@ and a per-query exclusion CSR, fused so that the score matrix is never written.
 TopKMetrics (dcue_topk_metrics) says how good TopK's lists are: Precision / Recall / NDCG / MAP / MRR /
 HitRate at several cutoffs and catalogue coverage against held-out truth rows, on the device lists.
 
+Diversify (dcue_list_mmr / dcue_list_ild) trades relevance against redundancy: Maximal Marginal Relevance
+re-ranking of TopK's device lists, and their intra-list diversity next to TopKMetrics' numbers.
+
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
@@ -200,6 +203,7 @@ class TopK(_Workspace):
     raw rows, dcue_topk_scored: what WRMF factors are ranked by)."""
 
     DEFAULT_QUERY_BATCH = 4096
+    _div = None  # the Diversify of diversity= calls, made at the first one
 
     def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None, score="cosine"):
         self.device = torch.device(device)
@@ -217,9 +221,32 @@ class TopK(_Workspace):
     def _nonfinite(self, queries, bad):
         return (_nonfinite_error if self.score == nat.SCORE_COSINE else _nonfinite_dot_error)(queries, bad)
 
-    def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
+    def _diverse_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel):
+        """topk_raw at k = pool, then Diversify.mmr_raw down to k. The flags are dcue_topk's; a list MMR
+        found non-finite (nat.LIST_FLAG_NONFINITE) carries dcue_topk's bit for it."""
+        k, pool = check_pool(k, pool)
+        if rel is None:
+            rel = "raw" if self.score == nat.SCORE_COSINE else "minmax"
+        if self._div is None:
+            self._div = Diversify(self.device)
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split)
+        idx, score, count, mflags = self._div.mmr_raw(idx, score, count, cand_feat, k, diversity, rel)
+        return idx, score, count, flags | ((mflags & nat.LIST_FLAG_NONFINITE) >> 1)
+
+    def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
+                 rel=None):
         """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
-        as dcue_topk writes them (no non-finite check)."""
+        as dcue_topk writes them (no non-finite check).
+
+        diversity (lambda in [0, 1]; None: the plain relevance ranking, today's path exactly): the
+        `pool` best candidates are ranked (default min(128, 4 k); k <= pool <= 128) and re-ranked down
+        to k by Maximal Marginal Relevance on the device (Diversify.mmr_raw, include/dcue.h
+        dcue_list_mmr). rel: "raw" / "minmax" relevance scaling, default raw for cosine scores and
+        minmax for dot. The scores returned are the entries' original ones."""
+        if diversity is not None:
+            return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel)
+        if pool is not None or rel is not None:
+            raise ValueError("pool and rel belong to diversity=, which is not set")
         nat.require_gpu(query_feat, "query_feat")
         nat.require_gpu(cand_feat, "cand_feat")
         query_feat = query_feat.contiguous().float()
@@ -250,14 +277,17 @@ class TopK(_Workspace):
                 nat.check(nat.lib().dcue_topk_scored(self.score, *args), "dcue_topk_scored")
         return idx[:nq], score[:nq], count[:nq], flags[:nq]
 
-    def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0):
+    def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
+             rel=None):
         """(idx int64 [n, k], score float32 [n, k], count int32 [n]) numpy arrays, best first; rows
-        with fewer than k eligible candidates end in idx -1 / score -inf.
+        with fewer than k eligible candidates end in idx -1 / score -inf. diversity / pool / rel: as
+        topk_raw (the lists are then in MMR's selection order, not sorted by score).
 
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite: a diverged model fails here as it fails in DCUE.score (score="dot": the factors are
         not finite or the product overflowed)."""
-        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split)
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split,
+                                                 diversity, pool, rel)
         flags = flags.cpu().numpy()
         bad = (flags & 2).astype(bool)
         if bad.any():
@@ -275,6 +305,124 @@ def check_cutoffs(ks):
     if ks[0] < 1 or ks[-1] > nat.TOPK_MAX_K:
         raise ValueError("cutoffs must be in 1..%d, got %s" % (nat.TOPK_MAX_K, ks))
     return ks
+
+
+def check_pool(k, pool):
+    """(k, pool) as ints for a diversity= call: pool defaults to min(128, 4 k); ValueError naming the
+    limits otherwise."""
+    k = int(k)
+    if not 1 <= k <= nat.TOPK_MAX_K:
+        raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, k))
+    pool = min(nat.TOPK_MAX_K, 4 * k) if pool is None else int(pool)
+    if not k <= pool <= nat.TOPK_MAX_K:
+        raise ValueError("pool must be in k..%d (k = %d), got %d" % (nat.TOPK_MAX_K, k, pool))
+    return k, pool
+
+
+class Diversify(_Workspace):
+    """Maximal Marginal Relevance re-ranking and intra-list diversity of the lists dcue_topk leaves on
+    the device (include/dcue.h dcue_list_mmr / dcue_list_ild / dcue_list_ild_mean): device tensors in
+    and out, one kernel launch per call, no list is copied to the host."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def _device_lists(self, idx, count, cand_feat, score=None):
+        nat.require_gpu(idx, "idx")
+        nat.require_gpu(count, "count")
+        nat.require_gpu(cand_feat, "cand_feat")
+        if idx.dim() != 2 or idx.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() != idx.shape[0]:
+            raise ValueError("idx must be int32 [n, k] and count int32 [n]")
+        if not 1 <= idx.shape[1] <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, idx.shape[1]))
+        if cand_feat.dim() != 2 or cand_feat.shape[0] < 1 or not 1 <= cand_feat.shape[1] <= 256:
+            raise ValueError("candidate factors must be [n_cand, d] with d in 1..256, got %s"
+                             % (tuple(cand_feat.shape),))
+        if score is not None:
+            nat.require_gpu(score, "score")
+            if score.dtype != torch.float32 or score.shape != idx.shape:
+                raise ValueError("score must be float32 %s like idx, got %s %s"
+                                 % (tuple(idx.shape), score.dtype, tuple(score.shape)))
+            score = score.contiguous()
+        return idx.contiguous(), count.contiguous(), cand_feat.contiguous().float(), score
+
+    def _workspace(self, pool, d, n):
+        """(pointer, bytes) of the grown workspace; (None, 0) while the kernels need none."""
+        nbytes = self._nbytes("dcue_list_mmr_workspace_bytes", pool, d, n)
+        return (nat.ptr(self._grow(nbytes)), nbytes) if nbytes else (None, 0)
+
+    def mmr_raw(self, idx, score, count, cand_feat, k, lambda_, rel="raw"):
+        """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors: the
+        pools idx int32 [n, pool] / score float32 [n, pool] / count int32 [n] (as dcue_topk writes them)
+        re-ranked down to k by MMR with lambda = lambda_ over the cosine of cand_feat's rows. rel: "raw"
+        or "minmax". score is each entry's original one; flags: nat.LIST_FLAG_BAD_INDEX /
+        LIST_FLAG_NONFINITE (such a list comes back empty)."""
+        idx, count, cand_feat, score = self._device_lists(idx, count, cand_feat, score)
+        n, pool, k, lam = int(idx.shape[0]), int(idx.shape[1]), int(k), float(lambda_)
+        if not 1 <= k <= pool:
+            raise ValueError("k must be in 1..%d (the pool), got %d" % (pool, k))
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("lambda must be in [0, 1], got %r" % (lambda_,))
+        if rel not in nat.MMR_RELS:
+            raise ValueError("rel must be one of %s, got %r" % (sorted(nat.MMR_RELS), rel))
+        out_idx = torch.full((max(n, 1), k), -1, dtype=torch.int32, device=self.device)
+        out_score = torch.full((max(n, 1), k), float("-inf"), dtype=torch.float32, device=self.device)
+        out_count = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        if n:
+            d = int(cand_feat.shape[1])
+            ws, ws_bytes = self._workspace(pool, d, n)
+            nat.check(nat.lib().dcue_list_mmr(
+                nat.ptr(idx), nat.ptr(score), nat.ptr(count), n, pool, nat.ptr(cand_feat), int(cand_feat.shape[0]), d,
+                lam, nat.MMR_RELS[rel], k, ws, ws_bytes, nat.ptr(out_idx), nat.ptr(out_score), nat.ptr(out_count),
+                nat.ptr(flags), nat.stream_handle(self.device)), "dcue_list_mmr")
+        return out_idx[:n], out_score[:n], out_count[:n], flags[:n]
+
+    def _ild_into(self, idx, count, cand_feat, ks, cut, out, flags):
+        """dcue_list_ild on checked device lists, writing out [n, m] / flags [n] (views of the caller's buffers)."""
+        n, k, d = int(idx.shape[0]), int(idx.shape[1]), int(cand_feat.shape[1])
+        if ks[-1] > k:
+            raise ValueError("cutoff %d is beyond the lists' k = %d" % (ks[-1], k))
+        if n:
+            ws, ws_bytes = self._workspace(k, d, n)
+            nat.check(nat.lib().dcue_list_ild(
+                nat.ptr(idx), nat.ptr(count), n, k, nat.ptr(cand_feat), int(cand_feat.shape[0]), d,
+                ctypes.cast(cut, ctypes.c_void_p), len(ks), ws, ws_bytes, nat.ptr(out), nat.ptr(flags),
+                nat.stream_handle(self.device)), "dcue_list_ild")
+
+    def ild_raw(self, idx, count, cand_feat, ks):
+        """(ild float64 [n, m], flags int32 [n]) device tensors: the intra-list diversity of the lists
+        idx int32 [n, k] / count int32 [n] at the sorted distinct cutoffs of ks. flags:
+        nat.LIST_FLAG_NO_PAIR (a cutoff with fewer than two entries: its value is 0) / LIST_FLAG_BAD_INDEX /
+        LIST_FLAG_NONFINITE."""
+        ks = check_cutoffs(ks)
+        cut = (ctypes.c_int32 * len(ks))(*ks)
+        idx, count, cand_feat, _ = self._device_lists(idx, count, cand_feat)
+        n = int(idx.shape[0])
+        out = torch.zeros((max(n, 1), len(ks)), dtype=torch.float64, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        self._ild_into(idx, count, cand_feat, ks, cut, out, flags)
+        return out[:n], flags[:n]
+
+    def ild_mean_raw(self, ild, flags):
+        """(mean float64 [m], n_evaluated int32 [1]) device tensors: dcue_list_ild_mean over ild [n, m] /
+        flags [n] -- the mean over the unflagged lists, in an order that depends on n and m only."""
+        nat.require_gpu(ild, "ild")
+        nat.require_gpu(flags, "flags")
+        if ild.dim() != 2 or ild.dtype != torch.float64 or flags.dtype != torch.int32 or flags.numel() != ild.shape[0]:
+            raise ValueError("ild must be float64 [n, m] and flags int32 [n]")
+        n, m = int(ild.shape[0]), int(ild.shape[1])
+        if not 1 <= m <= nat.TOPK_METRICS_MAX_CUTOFFS:
+            raise ValueError("at most %d cutoffs per call, got %d" % (nat.TOPK_METRICS_MAX_CUTOFFS, m))
+        mean = torch.zeros(m, dtype=torch.float64, device=self.device)
+        n_eval = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if n == 0:  # (an empty tensor's address may be null)
+            ild = torch.zeros((1, m), dtype=torch.float64, device=self.device)
+            flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().dcue_list_ild_mean(nat.ptr(ild.contiguous()), nat.ptr(flags.contiguous()), n, m,
+                                               nat.ptr(mean), nat.ptr(n_eval), nat.stream_handle(self.device)),
+                  "dcue_list_ild_mean")
+        return mean, n_eval
 
 
 class TopKMetrics(_Workspace):
@@ -359,18 +507,28 @@ class TopKMetrics(_Workspace):
             nat.stream_handle(self.device)), "dcue_topk_metrics_mean")
         return mean, cov, n_eval
 
-    def evaluate(self, query_feat, cand_feat, queries, ks, query_batch=None, per_query=False):
+    def evaluate(self, query_feat, cand_feat, queries, ks, query_batch=None, per_query=False, diversity=None,
+                 pool=None, rel=None, ild=False):
         """{"ks", "n_evaluated", "precision", "recall", "ndcg", "map", "mrr", "hit", "coverage"}: each
         metric a float64 array over the cutoffs, the mean over the queries with a non-empty truth row;
         per_query adds "per_query" (numpy [n, m, 6], slots in nat.TOPK_METRIC_NAMES order) and "flags".
         Query batches go through TopK.topk_raw with k = max(ks) and dcue_topk_metrics on its device
         tensors; one dcue_topk_metrics_mean call ends it. The result does not depend on query_batch.
 
+        diversity / pool / rel: the lists are TopK.topk_raw's MMR re-ranked ones (k = max(ks)); None
+        scores today's lists. ild adds "ild" (float64 over the cutoffs: the mean intra-list diversity
+        of the lists that were scored, over those with at least two entries at every cutoff) and
+        "n_ild" (their number), by dcue_list_ild / dcue_list_ild_mean on the same device lists.
+
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite, as TopK.topk does."""
         ks, cut = self._cutoffs(ks)
         queries = np.asarray(queries, dtype=np.int64).reshape(-1)
         n, m, k = len(queries), len(ks), ks[-1]
+        if diversity is not None:
+            check_pool(k, pool)
+        elif pool is not None or rel is not None:
+            raise ValueError("pool and rel belong to diversity=, which is not set")
         if self.topk.excl_ptr is None and query_feat.shape[0] != self.n_query_rows:
             raise ValueError("query factors have %d rows, the truth CSR %d" % (query_feat.shape[0], self.n_query_rows))
         qb = int(self.topk.DEFAULT_QUERY_BATCH if query_batch is None else query_batch)
@@ -380,12 +538,23 @@ class TopKMetrics(_Workspace):
         flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         nonfinite = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         exposure = self.new_exposure(m)
+        if ild:
+            div = Diversify(self.device)
+            ild_out = torch.zeros((max(n, 1), m), dtype=torch.float64, device=self.device)
+            ild_flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         for q0 in range(0, n, qb):
             part = queries[q0:q0 + qb]
-            idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb)
+            if diversity is None:
+                idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb)
+            else:
+                idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb,
+                                                           diversity=diversity, pool=pool, rel=rel)
             q = torch.as_tensor(part.astype(np.int32)).to(self.device)
             self._metrics_into(idx, count, q, cut, m, out[q0:], flags[q0:], exposure)
             nonfinite[q0:q0 + len(part)] = tflags
+            if ild:
+                lists = div._device_lists(idx, count, cand_feat)
+                div._ild_into(*lists[:3], ks, cut, ild_out[q0:], ild_flags[q0:])
         bad = (nonfinite[:n].cpu().numpy() & 2).astype(bool)
         if bad.any():
             raise self.topk._nonfinite(queries, bad)
@@ -395,6 +564,10 @@ class TopKMetrics(_Workspace):
         for s, name in enumerate(nat.TOPK_METRIC_NAMES):
             res[name] = mean[:, s].copy()
         res["coverage"] = cov.cpu().numpy()
+        if ild:
+            ild_mean, n_ild = div.ild_mean_raw(ild_out[:n], ild_flags[:n])
+            res["ild"] = ild_mean.cpu().numpy()
+            res["n_ild"] = int(n_ild.cpu().numpy()[0])
         if per_query:
             res["per_query"] = out[:n].cpu().numpy()
             res["flags"] = flags[:n].cpu().numpy()

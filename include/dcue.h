@@ -781,6 +781,70 @@ int dcue_topk_metrics_mean(const double* metrics, const int32_t* flags, int32_t 
                            int64_t n_cand, double* out_mean, double* out_coverage,
                            int32_t* out_n_evaluated, void* stream);
 
+/* ------------------------------------------- diversity-aware serving: MMR, ILD (added under ABI 17) */
+/* Maximal Marginal Relevance re-ranking (Carbonell & Goldstein, SIGIR 1998) of the lists dcue_topk /
+ * dcue_topk_scored leave on the device, and the intra-list diversity of such lists. The reference has
+ * no counterpart.
+ * Pool. A list L[0..c) of candidate indices with relevances r[0..c): dcue_topk's out_idx / out_score /
+ *   out_count at k = pool, 1 <= pool <= DCUE_TOPK_MAX_K; c = count clamped to 0..pool. Entries at j >= c
+ *   are never read. Pool POSITIONS are the entities: a caller-supplied list that names an index twice
+ *   has two entries with similarity 1.
+ * Similarity. sim(a, b) = the cosine of rows L[a], L[b] of cand_feat [n_cand][d], d <= 256, with the
+ *   project's clamp x / max(||x||, 1e-8) on each side, in fp32: (x_a . x_b) * (inv_a * inv_b), inv = 1 /
+ *   max(sqrt(x . x), 1e-8), the norms read from the Gram matrix's diagonal. A zero row has similarity 0
+ *   to everything. Always the cosine, also for DCUE_SCORE_DOT lists. sim(a, b) and sim(b, a) are the
+ *   same bits.
+ * Relevance scaling (rel_mode). DCUE_MMR_REL_RAW: r' = r (cosine lists are on the similarity's scale).
+ *   DCUE_MMR_REL_MINMAX: r' = (r - min r) / (max r - min r) over the list's c entries, 0 when max == min
+ *   (inner-product lists, whose scale is arbitrary); fp32, in exactly this order.
+ * Selection. S starts empty; m_a = 0 while S is empty, afterwards m_a = max_{b in S} sim(a, b) (which
+ *   may be negative). For t = 0 .. min(k_out, c) - 1 the unselected position a that maximises
+ *   f_a = lambda * r'_a - (1 - lambda) * m_a is selected (fp32, every operation rounded on its own);
+ *   ties go to the LOWEST pool position -- with dcue_topk's order a total order. 0 <= lambda <= 1;
+ *   lambda = 1 returns the first k_out entries of the pool unchanged.
+ * Outputs. out_idx [n_lists][k_out], out_score [n_lists][k_out] (the entry's original r, never r' or f),
+ *   out_count [n_lists] = min(k_out, c); short lists end in idx -1 / score -inf as dcue_topk's do.
+ *   out_flags[i] bit 1 (DCUE_LIST_FLAG_BAD_INDEX): an entry L[j], j < c, lies outside [0, n_cand) --
+ *   each entry is range-checked before it addresses anything; bit 2 (DCUE_LIST_FLAG_NONFINITE): a pool
+ *   row or a relevance is NaN or infinite (or a row's squared norm overflows fp32). A flagged list gets
+ *   count 0 and all padding.
+ * ILD. For a list and a cutoff K, n_K = min(K, c):
+ *   ILD@K = 2 / (n_K (n_K - 1)) * sum_{a < b < n_K} (1 - sim(a, b)),
+ *   fp64 sums over the fp32 similarities in a fixed order (per b ascending a, then ascending b). Where
+ *   n_K < 2 the value is 0 and bit 0 (DCUE_LIST_FLAG_NO_PAIR) is set for the list -- so a call whose
+ *   cutoffs include 1 flags every list. out_ild [n_lists][n_cutoffs]; bits 1 and 2 as above, all values
+ *   0. dcue_list_ild_mean: out_mean[i] = the arithmetic mean of column i over the lists with flags == 0,
+ *   *out_n_evaluated their number (means 0 where it is 0); one workgroup, an order that depends on
+ *   n_lists and n_cutoffs only: bit-identical however `ild` was filled.
+ * Invariance. A list's outputs are a function of that list and the rows it names: they do not depend on
+ *   n_lists, on batching, or on which other lists share the launch, bit for bit. The Gram summation
+ *   order depends on d alone.
+ * cutoffs_host[n_cutoffs] (HOST memory): 1 <= k_1 < ... < k_m <= k, 1 <= m <= 8.
+ * The kernels keep a list's rows and its similarity matrix in LDS and need no workspace:
+ * dcue_list_mmr_workspace_bytes (a host computation; dcue_list_ild's too, with pool = k) gives 0 today,
+ * and ws may then be null; the parameters stay so that this can change without the ABI.
+ * All calls are asynchronous on `stream` and validate every argument on the host before their first
+ * device call (DCUE_ERR_INVALID: a null required pointer, pool or k outside 1..DCUE_TOPK_MAX_K, k_out
+ * outside 1..pool, lambda outside [0, 1] or NaN, an unknown rel_mode, cutoffs not strictly ascending /
+ * below 1 / above k, n_cutoffs outside 1..8, n_cand <= 0, d <= 0, n_lists < 0; DCUE_ERR_UNSUPPORTED:
+ * d > 256, n_cand beyond dcue_topk's bound; DCUE_ERR_WORKSPACE). n_lists == 0 is DCUE_OK. */
+#define DCUE_MMR_REL_RAW 0
+#define DCUE_MMR_REL_MINMAX 1
+#define DCUE_LIST_FLAG_NO_PAIR 1
+#define DCUE_LIST_FLAG_BAD_INDEX 2
+#define DCUE_LIST_FLAG_NONFINITE 4
+int dcue_list_mmr_workspace_bytes(int32_t pool, int32_t d, int32_t n_lists, size_t* bytes_host);
+int dcue_list_mmr(const int32_t* idx, const float* score, const int32_t* count, int32_t n_lists,
+                  int32_t pool, const float* cand_feat, int64_t n_cand, int32_t d, float lambda,
+                  int32_t rel_mode, int32_t k_out, void* ws, size_t ws_bytes, int32_t* out_idx,
+                  float* out_score, int32_t* out_count, int32_t* out_flags, void* stream);
+int dcue_list_ild(const int32_t* idx, const int32_t* count, int32_t n_lists, int32_t k,
+                  const float* cand_feat, int64_t n_cand, int32_t d, const int32_t* cutoffs_host,
+                  int32_t n_cutoffs, void* ws, size_t ws_bytes, double* out_ild /* [n][m] */,
+                  int32_t* out_flags, void* stream);
+int dcue_list_ild_mean(const double* ild, const int32_t* flags, int32_t n_lists, int32_t n_cutoffs,
+                       double* out_mean /* [m] */, int32_t* out_n_evaluated, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

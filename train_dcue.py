@@ -10,6 +10,10 @@ this is that driver for the MI355X build:
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-for new.csv
                                                   # the top 10 of users outside the training set
   python train_dcue.py ... --eval-k 10,50,100 --eval-out metrics.json     # + top-K ranking metrics
+  python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-diversity 0.7
+                                                  # MMR re-ranked lists (--recommend-pool: the pool)
+  python train_dcue.py ... --eval-k 10,50 --eval-out metrics.json --eval-ild --eval-diversity 0.7
+                                                  # + intra-list diversity, of the MMR re-ranked lists
 
 triplets: (user_id, song_id, score) by column position (datasets/dcuedataset.py:229,238);
 metadata: song_id in column 1 and a `data_mel` column of torch.save'd [128, T] tensors
@@ -61,10 +65,19 @@ def parse(argv=None):
                     help="columns user_id,song_id: histories of users outside the training set; their "
                          "lists (DCUE.recommend_for: fold-in, then top K) are written instead of the "
                          "training users'")
+    ap.add_argument("--recommend-diversity", type=float, metavar="L",
+                    help="MMR re-ranking of the --recommend-k / --recommend-for lists with lambda = L in [0, 1] "
+                         "(DCUE.recommend(diversity=L)); default: the plain ranking")
+    ap.add_argument("--recommend-pool", type=int, metavar="P",
+                    help="candidates ranked per user before the MMR pass (K..128; default min(128, 4 K))")
     ap.add_argument("--eval-k", metavar="K[,K...]",
                     help="after training, Precision / Recall / NDCG / MAP / MRR / HitRate / coverage at these "
                          "cutoffs over the val and the test split (DCUE.evaluate_topk)")
     ap.add_argument("--eval-out", help="JSON for --eval-k: {\"val\": {...}, \"test\": {...}}")
+    ap.add_argument("--eval-ild", action="store_true",
+                    help="--eval-k also reports ild@K, the lists' mean intra-list diversity")
+    ap.add_argument("--eval-diversity", type=float, metavar="L",
+                    help="--eval-k scores the MMR re-ranked lists (lambda = L) instead of the plain ranking")
     args = ap.parse_args(argv)
     if bool(args.eval_k) != bool(args.eval_out):
         ap.error("--eval-k and --eval-out go together")
@@ -77,6 +90,16 @@ def parse(argv=None):
         ap.error("--recommend-k and --recommend-out go together")
     if args.recommend_for and not args.recommend_out:
         ap.error("--recommend-for needs --recommend-k and --recommend-out")
+    if (args.recommend_diversity is not None or args.recommend_pool is not None) and args.recommend_k <= 0:
+        ap.error("--recommend-diversity / --recommend-pool need --recommend-k")
+    if args.recommend_pool is not None and args.recommend_diversity is None:
+        ap.error("--recommend-pool needs --recommend-diversity")
+    if (args.eval_ild or args.eval_diversity is not None) and not args.eval_k:
+        ap.error("--eval-ild / --eval-diversity need --eval-k")
+    for name in ("recommend_diversity", "eval_diversity"):
+        lam = getattr(args, name)
+        if lam is not None and not 0.0 <= lam <= 1.0:
+            ap.error("--%s takes a lambda in [0, 1], got %r" % (name.replace("_", "-"), lam))
     return args
 
 
@@ -139,33 +162,38 @@ def main(argv=None):
             new = pd.read_csv(args.recommend_for, dtype=str)
             histories = {u: list(g) for u, g in new.groupby("user_id", sort=False)["song_id"]}
             write_recommendations(dcue, list(histories), args.recommend_k, args.recommend_out,
-                                  histories=histories, seed=args.seed)
+                                  histories=histories, seed=args.seed, diversity=args.recommend_diversity,
+                                  pool=args.recommend_pool)
         else:
-            write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out)
+            write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out,
+                                  diversity=args.recommend_diversity, pool=args.recommend_pool)
     if args.eval_k:
-        write_metrics(dcue, val, test, args.eval_k, args.eval_out)
+        write_metrics(dcue, val, test, args.eval_k, args.eval_out, diversity=args.eval_diversity, ild=args.eval_ild)
     return dcue
 
 
-def write_metrics(dcue, val, test, ks, path):
-    """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs."""
+def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False):
+    """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs
+    (diversity: of the MMR re-ranked lists; ild: with their intra-list diversity)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
-    res = {"val": dcue.evaluate_topk(val, ks=ks), "test": dcue.evaluate_topk(test, ks=ks)}
+    res = {"val": dcue.evaluate_topk(val, ks=ks, diversity=diversity, ild=ild),
+           "test": dcue.evaluate_topk(test, ks=ks, diversity=diversity, ild=ild)}
     with open(path, "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
         f.write("\n")
 
 
-def write_recommendations(dcue, users, k, path, histories=None, seed=0):
+def write_recommendations(dcue, users, k, path, histories=None, seed=0, diversity=None, pool=None):
     """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank).
-    histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for)."""
+    histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for).
+    diversity / pool: MMR re-ranked lists (DCUE.recommend)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
     if histories is not None:
-        lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed)
+        lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed, diversity=diversity, pool=pool)
     else:
-        lists = dcue.recommend(users, k=k)
+        lists = dcue.recommend(users, k=k, diversity=diversity, pool=pool)
     rows = [(u, r + 1, song, score) for u, lst in zip(users, lists) for r, (song, score) in enumerate(lst)]
     pd.DataFrame(rows, columns=["user_id", "rank", "song_id", "score"]).to_csv(path, index=False)
 
