@@ -14,6 +14,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace dcue {
 // records the failing HIP call for dcue_last_error() (timer.hip)
 void set_last_error(const char* expr, hipError_t e, const char* file, int line);
+// the same slot for a call that refuses its arguments with a reason (dcue_logmel)
+void set_last_message(const char* text);
 }  // namespace dcue
 
 #define DCUE_HIP_CHECK(expr)                                      \

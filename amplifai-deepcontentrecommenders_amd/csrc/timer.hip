@@ -183,6 +183,8 @@ void set_last_error(const char* expr, hipError_t e, const char* file, int line) 
            hipGetErrorString(e), (int)e);
 }
 
+void set_last_message(const char* text) { snprintf(g_last_error, sizeof(g_last_error), "%s", text); }
+
 }  // namespace dcue
 
 extern "C" const char* dcue_last_error(void) { return dcue::g_last_error; }

@@ -111,6 +111,18 @@ class FoldinConfig(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+class LogmelConfig(ctypes.Structure):
+    """dcue_logmel_config (the audio front end, added under ABI 17)."""
+    _fields_ = [("sample_rate", ctypes.c_int32), ("n_fft", ctypes.c_int32), ("hop", ctypes.c_int32),
+                ("center", ctypes.c_int32), ("compress", ctypes.c_int32), ("out_dtype", ctypes.c_int32),
+                ("fmin", ctypes.c_float), ("fmax", ctypes.c_float), ("amin", ctypes.c_float),
+                ("log_scale", ctypes.c_float)]
+
+
+LOGMEL_POWER, LOGMEL_DB, LOGMEL_LOG1P = 0, 1, 2  # DCUE_LOGMEL_*
+LOGMEL_MODES = {"power": LOGMEL_POWER, "db": LOGMEL_DB, "log1p": LOGMEL_LOG1P}
+LOGMEL_FLAG_NONFINITE = 1
+LOGMEL_N_FFT = (256, 512, 1024, 2048)
 FOLDIN_MAX_STEPS, FOLDIN_MAX_NEG, FOLDIN_MAX_POS = 4096, 256, 1024
 FOLDIN_EMPTY, FOLDIN_NONFINITE, FOLDIN_DROPPED = 1, 2, 4  # out_flags bits
 MT_STATE_BYTES = 624 * 4 + 16
@@ -236,6 +248,13 @@ _SIGS = {
                           ctypes.POINTER(FoldinConfig), _P, _P, ctypes.c_size_t, _P, _P, _P, _P, _P], ctypes.c_int),
     "dcue_foldin_negatives": ([ctypes.c_int64, _P, _P, _P, ctypes.c_int32, ctypes.c_int64,
                                ctypes.POINTER(FoldinConfig), ctypes.c_int32, _P, _P], ctypes.c_int),
+    "dcue_logmel_frames": ([ctypes.POINTER(LogmelConfig), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+                           ctypes.c_int),
+    "dcue_logmel_table_bytes": ([ctypes.POINTER(LogmelConfig), ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_logmel_table_fill_host": ([ctypes.POINTER(LogmelConfig), _P, ctypes.c_size_t], ctypes.c_int),
+    "dcue_logmel_table_init": ([ctypes.POINTER(LogmelConfig), _P, ctypes.c_size_t, _P], ctypes.c_int),
+    "dcue_logmel": ([ctypes.POINTER(LogmelConfig), _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                     ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     "dcue_debug_delay": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "dcue_debug_probes": ([_P], ctypes.c_int),
     "dcue_debug_probe_count": ([], ctypes.c_int),
@@ -279,7 +298,7 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
-        if status == 3:
+        if status == 3 or what.startswith("dcue_logmel"):  # the calls that leave a dcue_last_error text
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 

@@ -593,6 +593,61 @@ class DCUE(Trainer):
         feat = self._item_feat_by_index()
         return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
 
+    # ------------------------------------------------------------------ unseen songs
+    def embed_audio(self, wave, logmel=None, frame0=0):
+        """[n, d] item factors of waveforms ([n_samples] or [n, n_samples], mono, at the front end's
+        sample rate) -- the cold-start step for a song nobody has played: audio.LogMel.track_rows writes
+        a temporary fp16 track table on the GPU (frames frame0 .. frame0 + 130 of each clip) and
+        dcue_item_tower_eval reads it where it lies. Needs no dataset and no host copy. logmel: an
+        audio.LogMel (default: one with the default configuration, kept for later calls). A clip with a
+        NaN or infinite sample raises ValueError naming it."""
+        from dcrecommend import audio
+        if self.model._flat["dims"].tower == nat.TOWERS[nat.TEXT_TOWER]:
+            raise RuntimeError("embed_audio: the text tower needs a song's tokens too; audio alone is not enough")
+        if logmel is None:
+            if getattr(self, "_logmel", None) is None:
+                self._logmel = audio.LogMel(device=self.device)
+            logmel = self._logmel
+        self.model.eval()
+        self.model._require_device()
+        table = logmel.track_rows(wave, frame0, torch.float16)
+        n = int(table.shape[0])
+        ds = nat.storage_dims(self.model._flat["dims"]).feature_dim
+        feat = torch.empty((max(n, 1), ds), device=self.device)
+        if n:
+            tr = nat.Tracks(table.data_ptr(), n, 0, 0)
+            it = torch.arange(n, dtype=torch.int32, device=self.device)
+            model = self.model._model_struct()
+            ws = self._factor_ws(1, n)
+            nat.check(nat.lib().dcue_item_tower_eval(ctypes.byref(model), ctypes.byref(tr), nat.ptr(it), n,
+                                                     nat.ptr(ws), ws.numel(), nat.ptr(feat), nat.stream_handle()),
+                      "dcue_item_tower_eval")
+        return feat[:n, :self.feature_dim].contiguous()
+
+    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None):
+        """The k catalogue songs nearest to each clip, by the cosine of its embed_audio factor to the
+        item factors: one list of (song_id, score) pairs per clip, as similar_songs returns (nothing is
+        excluded: the clip is not in the catalogue)."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        q = self.embed_audio(wave, logmel)
+        out = self._topk("audio", ds, False).topk(q, self._item_feat_by_index(), np.arange(q.shape[0]), k)
+        return self._as_pairs(ds, *out)
+
+    def listeners_for_audio(self, wave, k=10, logmel=None):
+        """The k users with the highest cosine to each clip -- "who should hear this": the clips'
+        embed_audio factors against user_factors on the same kernel. One list of (user_id, score) pairs
+        per clip, best first."""
+        self._require_factors()
+        q = self.embed_audio(wave, logmel)
+        key = ("topk", "listeners")
+        if key not in self._evals:
+            self._evals[key] = rank.TopK(None, None, None, self.device, n_cand=int(self.user_factors.shape[0]))
+        idx, score, count = self._evals[key].topk(q, self.user_factors, np.arange(q.shape[0]), k)
+        names = self._index_source(None).userindex2userid
+        return [[(names[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
+                for r in range(len(count))]
+
     # ------------------------------------------------------------------ list quality
     def _topk_metrics(self, ds):
         """rank.TopKMetrics per dataset, cached as _topk caches its lists, and the user rows with a

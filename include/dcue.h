@@ -845,6 +845,62 @@ int dcue_list_ild(const int32_t* idx, const int32_t* count, int32_t n_lists, int
 int dcue_list_ild_mean(const double* ild, const int32_t* flags, int32_t n_lists, int32_t n_cutoffs,
                        double* out_mean /* [m] */, int32_t* out_n_evaluated, void* stream);
 
+/* ------------------------------------------- audio front end: waveform -> log-mel (added under ABI 17) */
+/* The step before the item tower: mono f32 waveforms in, [frame][DCUE_N_MELS] track-table rows out, in
+ * one launch -- framing, window, FFT, power, mel filterbank and compression fused; no spectrum goes to
+ * HBM and there is no workspace. The reference has no counterpart (its README names a
+ * transform_audio.py that was never published), so the definition below is this project's own.
+ * Signal. With N = n_fft, pad = N/2 when center = 1 (the clip is reflect-padded: sample -i is sample
+ *   i, sample n_samples - 1 + i is sample n_samples - 1 - i) and 0 when center = 0, frame t is samples
+ *   [t hop - pad, t hop - pad + N) times the periodic Hann window 0.5 - 0.5 cos(2 pi n / N); a clip has
+ *   1 + (n_samples + 2 pad - N) / hop frames (22050 Hz, N 1024, hop 512, center: 66,560 samples give
+ *   DCUE_N_FRAMES = 131). S = |rfft|^2, N/2 + 1 bins. Mel bin i of 128 is sum_k w_i[k] S[k]: band edges
+ *   f_0..f_129 equally spaced on the Slaney mel scale (linear, 200/3 Hz per mel, below 1 kHz; above,
+ *   27 mel per factor 6.4) from fmin to fmax, triangles min((f - f_i) / (f_{i+1} - f_i), (f_{i+2} - f) /
+ *   (f_{i+2} - f_{i+1})) clipped at 0, times 2 / (f_{i+2} - f_i) -- librosa's defaults. The sum runs over
+ *   the bin's FFT bins in ascending order, always: a row's bits are a function of the frame's samples and
+ *   the table alone (not of n_clips, frame0, or what shares the launch).
+ * Compression. DCUE_LOGMEL_POWER: P. DCUE_LOGMEL_DB: 10 log10(max(P, amin)) (ref = 1.0); P <= amin gives
+ *   the floor 10 log10(amin), rounded once from double. DCUE_LOGMEL_LOG1P: log(1 + log_scale sqrt(P)).
+ *   Computed in f32; out_dtype 0 converts to fp16 last (round to nearest even).
+ * wave [n_clips][n_samples] f32, already at sample_rate. out [n_clips][n_frames][128] of out_dtype: the
+ *   dcue_tracks layout, so with n_frames = DCUE_N_FRAMES `out` is a track table as it stands. The call
+ *   writes frames frame0 .. frame0 + n_frames - 1 of each clip. flags [n_clips] is zeroed by the call;
+ *   bit 0 (DCUE_LOGMEL_FLAG_NONFINITE) is set for a clip when a sample the requested frames read is NaN
+ *   or infinite; the other clips' rows are unaffected, bit for bit.
+ * Table. dcue_logmel_table_bytes bytes of device memory, filled once per configuration by
+ *   dcue_logmel_table_init (which synchronises `stream`): the window, the FFT twiddles, and the filters as
+ *   per-bin [first FFT bin, count) runs plus packed weights (a triangle is one contiguous run; a filter
+ *   narrower than the FFT's resolution is empty -- count 0 -- and its bin holds the floor: 20 of them at
+ *   n_fft 256 and 22050 Hz). dcue_logmel_table_fill_host writes the same bytes to host memory: every
+ *   entry computed in double precision and rounded once to f32, so the kernel calls no device
+ *   trigonometry. Layout: int32 header[8] {magic, n_fft, n_weights}; f32 window[N]; f32 pairs
+ *   exp(-2 pi i t / (N/2)), t < N/2; f32 pairs exp(-2 pi i k / N), k <= N/4; int32 first[128], count[128],
+ *   offset[128]; f32 weights[N + 2]. dcue_logmel must be given the table of the same configuration.
+ * Every call validates on the host before its first device call, so the refusals below are reachable
+ * without a GPU, each with a dcue_last_error text. DCUE_ERR_INVALID: n_fft outside {256, 512, 1024,
+ * 2048}; hop < 1 or hop > n_fft; sample_rate < 1; fmin < 0, fmax > sample_rate / 2 or fmin >= fmax; amin
+ * <= 0 with DB; an unknown compress / out_dtype / center; center = 1 with n_samples <= n_fft / 2 (the
+ * reflection is undefined); center = 0 with n_samples < n_fft; a negative count; a frame range that
+ * reaches past the clip's frame count (never padded silently); a null pointer. DCUE_ERR_UNSUPPORTED:
+ * n_samples beyond the 32-bit sample index. n_clips == 0 or n_frames == 0 is DCUE_OK. dcue_logmel is
+ * asynchronous on `stream`. */
+#define DCUE_LOGMEL_POWER 0   /* mel power, no compression (tests, callers with their own log) */
+#define DCUE_LOGMEL_DB    1   /* 10*log10(max(P, amin)), ref = 1.0 */
+#define DCUE_LOGMEL_LOG1P 2   /* log(1 + log_scale*sqrt(P)) */
+#define DCUE_LOGMEL_FLAG_NONFINITE 1
+typedef struct dcue_logmel_config {
+  int32_t sample_rate, n_fft, hop, center;   /* center: 1 = reflect-pad n_fft/2 each side, 0 = none */
+  int32_t compress, out_dtype;               /* out_dtype as dcue_tracks.dtype: 0 fp16, 1 fp32 */
+  float fmin, fmax, amin, log_scale;
+} dcue_logmel_config;
+int dcue_logmel_frames(const dcue_logmel_config* cfg, int64_t n_samples, int64_t* n_frames_host);
+int dcue_logmel_table_bytes(const dcue_logmel_config* cfg, size_t* bytes_host);
+int dcue_logmel_table_fill_host(const dcue_logmel_config* cfg, void* table_host, size_t bytes);
+int dcue_logmel_table_init(const dcue_logmel_config* cfg, void* table_dev, size_t bytes, void* stream);
+int dcue_logmel(const dcue_logmel_config* cfg, const void* table_dev, const float* wave, int64_t n_clips,
+                int64_t n_samples, int64_t frame0, int32_t n_frames, void* out, int32_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
