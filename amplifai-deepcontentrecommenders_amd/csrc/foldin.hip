@@ -28,6 +28,7 @@
 
 #include "dcue_internal.h"
 #include "bn0adam.h"
+#include "mix64.h"
 
 namespace dcue {
 
@@ -49,12 +50,7 @@ static int fi_tier(int E, int D) {
 }
 static int fi_ws_acts(int tier) { return tier == 0 ? 0 : tier == 1 ? 2 : 5; }
 
-__host__ __device__ __forceinline__ unsigned long long fi_mix(unsigned long long z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
+__host__ __device__ __forceinline__ unsigned long long fi_mix(unsigned long long z) { return mix64(z); }
 __host__ __device__ __forceinline__ unsigned long long fi_row_key(unsigned long long seed, long long r) {
   return fi_mix(seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(r + 1));
 }

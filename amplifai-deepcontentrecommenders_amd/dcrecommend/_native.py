@@ -119,6 +119,21 @@ class LogmelConfig(ctypes.Structure):
                 ("log_scale", ctypes.c_float)]
 
 
+class TrackStore(ctypes.Structure):
+    """dcue_track_store (full-length tracks for dcue_crop_tracks, added under ABI 17)."""
+    _fields_ = [("data", ctypes.c_void_p), ("frame_ptr", ctypes.c_void_p), ("n_tracks", ctypes.c_int64),
+                ("total_frames", ctypes.c_int64), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class CropConfig(ctypes.Structure):
+    """dcue_crop_config."""
+    _fields_ = [("mode", ctypes.c_int32), ("grid_j", ctypes.c_int32), ("grid_n", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("draw", ctypes.c_uint64)]
+
+
+CROP_FIRST, CROP_CENTER, CROP_GRID, CROP_RANDOM = 0, 1, 2, 3  # DCUE_CROP_*
+CROP_FLAG_BAD_EXTENT, CROP_FLAG_BAD_ROW = 1, 2
+CROP_FACTOR_DRAW0 = 1 << 32  # the item-factor passes' draws: 2^32 + j, apart from every epoch's
 LOGMEL_POWER, LOGMEL_DB, LOGMEL_LOG1P = 0, 1, 2  # DCUE_LOGMEL_*
 LOGMEL_MODES = {"power": LOGMEL_POWER, "db": LOGMEL_DB, "log1p": LOGMEL_LOG1P}
 LOGMEL_FLAG_NONFINITE = 1
@@ -255,6 +270,9 @@ _SIGS = {
     "dcue_logmel_table_init": ([ctypes.POINTER(LogmelConfig), _P, ctypes.c_size_t, _P], ctypes.c_int),
     "dcue_logmel": ([ctypes.POINTER(LogmelConfig), _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                      ctypes.c_int32, _P, _P, _P], ctypes.c_int),
+    "dcue_crop_tracks": ([ctypes.POINTER(TrackStore), ctypes.POINTER(CropConfig), _P, ctypes.c_int64, _P,
+                          ctypes.c_int32, _P, _P, _P], ctypes.c_int),
+    "dcue_crop_starts_host": ([ctypes.POINTER(CropConfig), _P, _P, ctypes.c_int64, _P], ctypes.c_int),
     "dcue_debug_delay": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "dcue_debug_probes": ([_P], ctypes.c_int),
     "dcue_debug_probe_count": ([], ctypes.c_int),
@@ -298,7 +316,7 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
-        if status == 3 or what.startswith("dcue_logmel"):  # the calls that leave a dcue_last_error text
+        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop")):  # the calls that leave a dcue_last_error text
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 
@@ -483,3 +501,49 @@ def debug_fail_flags():
     v = ctypes.c_uint32()
     check(lib().dcue_debug_fail_flags(ctypes.byref(v)), "dcue_debug_fail_flags")
     return v.value
+
+
+def crop_config(mode, seed=0, draw=0, grid_j=0, grid_n=1):
+    """dcue_crop_config for a DCUE_CROP_* mode (include/dcue.h has the window rule)."""
+    return CropConfig(int(mode), int(grid_j), int(grid_n), 0, int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1))
+
+
+def track_store(data, frame_ptr):
+    """dcue_track_store over data [total_frames][128] (fp16 / fp32) and frame_ptr int64 [n_tracks + 1],
+    both device tensors."""
+    if data.dtype not in (torch.float16, torch.float32) or frame_ptr.dtype != torch.int64:
+        raise ValueError("track store: data must be fp16 or fp32 and frame_ptr int64")
+    if data.dim() != 2 or data.shape[1] != N_MELS or not data.is_contiguous() or frame_ptr.numel() < 1:
+        raise ValueError("track store: data must be a contiguous [total_frames][%d]" % N_MELS)
+    return TrackStore(data.data_ptr(), frame_ptr.data_ptr(), frame_ptr.numel() - 1, data.shape[0],
+                      0 if data.dtype == torch.float16 else 1, 0)
+
+
+def crop_tracks(data, frame_ptr, cfg, out, rows=None, starts=None, flags=None, stream=None):
+    """dcue_crop_tracks: out [n_out][131][128] (fp16 / fp32) receives the window of track rows[i] (int32;
+    None: track i) of the store (data, frame_ptr). Returns the flags tensor (int32 [n_out], device)."""
+    n_out = int(out.shape[0])
+    if out.dim() != 3 or tuple(out.shape[1:]) != (N_FRAMES, N_MELS) or not out.is_contiguous():
+        raise ValueError("crop_tracks: out must be a contiguous [n][%d][%d]" % (N_FRAMES, N_MELS))
+    if rows is not None and (rows.dtype != torch.int32 or rows.numel() != n_out):
+        raise ValueError("crop_tracks: rows must be int32 [n_out]")
+    if flags is None:
+        flags = torch.empty(max(n_out, 1), dtype=torch.int32, device=out.device)
+    store = track_store(data, frame_ptr)
+    check(lib().dcue_crop_tracks(ctypes.byref(store), ctypes.byref(cfg), ptr(rows), n_out, ptr(out),
+                                 0 if out.dtype == torch.float16 else 1, ptr(starts), ptr(flags),
+                                 stream_handle(out.device) if stream is None else stream), "dcue_crop_tracks")
+    return flags[:n_out]
+
+
+def crop_starts_host(cfg, lengths, track_ids=None):
+    """dcue_crop_starts_host: the window's first frame for tracks of `lengths` frames at store indices
+    `track_ids` (default 0..n-1), as an int64 numpy array. No GPU needed."""
+    import numpy as np
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    ids = None if track_ids is None else np.ascontiguousarray(track_ids, dtype=np.int64)
+    out = np.zeros(len(lengths), dtype=np.int64)
+    check(lib().dcue_crop_starts_host(ctypes.byref(cfg), ctypes.c_void_p(lengths.ctypes.data),
+                                      None if ids is None else ctypes.c_void_p(ids.ctypes.data), len(lengths),
+                                      ctypes.c_void_p(out.ctypes.data)), "dcue_crop_starts_host")
+    return out

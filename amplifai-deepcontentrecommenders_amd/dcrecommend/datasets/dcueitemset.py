@@ -47,6 +47,24 @@ class DCUEItemset(DCUEDataset):
             dtype = torch.float16 if torch.equal(host.half().float(), host) else torch.float32
         return host.to(dtype).to(device)
 
+    def track_store(self, device, dtype=None):
+        """(data [total_frames][128], frame_ptr int64 [n_items + 1]) on `device`: every track at its
+        full length, in item-index order -- item i holds frames frame_ptr[i] .. frame_ptr[i+1] - 1, none for
+        a song without audio. No _sample: include/dcue.h dcue_crop_tracks cuts the 131-frame windows on
+        the GPU. dtype None: fp16 if lossless, else fp32, as track_table decides."""
+        parts, lengths = [], np.zeros(len(self.item_index), dtype=np.int64)
+        for i, m in enumerate(self.item_rows()):
+            if m < 0 or m not in self.metadata.index:
+                continue
+            X = torch.load(self.metadata.at[m, 'data_mel'], weights_only=True).float()
+            parts.append(X.t())
+            lengths[i] = X.shape[1]
+        host = torch.cat(parts).contiguous() if parts else torch.zeros((0, 128), dtype=torch.float32)
+        if dtype is None:
+            dtype = torch.float16 if torch.equal(host.half().float(), host) else torch.float32
+        frame_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64))
+        return host.to(dtype).to(device), frame_ptr.to(device)
+
     def item_rows(self):
         """metadata index of every item index (songid2metaindex over item_index), -1 if absent."""
         rows = np.full(len(self.item_index), -1, dtype=np.int64)

@@ -80,6 +80,9 @@ class TrainPlan:
         self._probes = ProbeCheck(dev) if check == "probe" else None
         self._check = StepCheck(dev) if check and check != "probe" else None
         self._n_users = int(fl["dims"].n_users)
+        # mirror of the library's lookahead state: a batch announced for the next launch, and inputs the
+        # last launch prepared from the track table for the launch after it (require_no_lookahead)
+        self._announced = self._prepared = False
 
     def _check_before(self, users, item_track):
         ck = self._check
@@ -119,6 +122,7 @@ class TrainPlan:
                                         self._stream if stream is None else stream)
         if st != 0:
             nat.check(st, "dcue_plan_launch")
+        self._prepared, self._announced = self._announced, False
         if self._check is not None:
             self._check_after()
 
@@ -148,6 +152,7 @@ class TrainPlan:
                                       ctypes.byref(args), self._stream if stream is None else stream)
         if st != 0:
             nat.check(st, "dcue_plan_step")
+        self._prepared, self._announced = self._announced, False
         # the step's last Adam work may still run on the library's user stream (include/dcue.h
         # dcue_plan_step); the model joins it before anything reads the parameters from torch
         self.net._pending_plan = self
@@ -175,7 +180,21 @@ class TrainPlan:
             return False
         nat.check(st, "dcue_plan_set_next")
         self._hold.append((None, item_track))
+        self._announced = item_track is not None
         return True
+
+    def require_no_lookahead(self):
+        """Raises unless the bound track table may be rewritten: no batch is announced (set_next) and the
+        last launch prepared no inputs ahead -- bn0 statistics and the conv-1 weight-gradient operand
+        computed from the table's rows, which the next launch would use in place of the new rows. The
+        trainer's epoch loop ends in that state (its last step announces nothing); DCUE._recrop checks
+        it instead of relying on the loop's shape. Follow with sync() before the rewrite."""
+        if self._announced or self._prepared:
+            raise RuntimeError("TrainPlan: a lookahead is pending (%s); the track table may only change at an "
+                               "epoch boundary, after a step that announced no next batch -- or withdraw it "
+                               "with set_next(None) and launch once more"
+                               % ("a batch is announced" if self._announced else "the last step prepared the "
+                                  "next batch's inputs from the table"))
 
     def set_comm(self, comm):
         """Data parallelism inside step(): with a distributed.NativeComm bound, each step() also

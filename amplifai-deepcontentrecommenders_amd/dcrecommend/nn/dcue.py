@@ -120,10 +120,24 @@ class DCUE(Trainer):
     def __init__(self, feature_dim=100, conv_hidden=128, batch_size=64, neg_batch_size=20, u_embdim=300,
                  margin=0.2, optimize='adam', lr=0.00001, beta_one=0.9, beta_two=0.99, eps=1e-8,
                  weight_decay=0, restart_period=30, t_mult=2, num_epochs=90, model_type='truedcuemel1dbn',
-                 eval_pct=0.025, val_pct=1.0, device=None, defer_embedding=True):
+                 eval_pct=0.025, val_pct=1.0, device=None, defer_embedding=True, crop='load', crop_seed=0,
+                 factor_crops='random'):
         """Arguments as nn/dcue.py:47-50; device (default cuda:current) and defer_embedding (the
-        bit-identical deferred user-table Adam, dcrecommend.optim.NativeAdam) are MI355X additions."""
+        bit-identical deferred user-table Adam, dcrecommend.optim.NativeAdam) are MI355X additions.
+
+        crop: 'load' cuts each track's 131-frame window once, when the catalogue is loaded. 'epoch'
+        keeps the full-length tracks in HBM (DCUEItemset.track_store) and re-cuts the whole table in
+        place before every training sub-epoch, a random window per track from (crop_seed, nn_epoch)
+        (include/dcue.h dcue_crop_tracks); the item factors then average n_iter real passes over
+        factor_crops windows: 'random' (the same draws every epoch) or 'grid' (evenly spread)."""
+        if crop not in ('load', 'epoch'):
+            raise ValueError("crop must be 'load' or 'epoch', got %r" % (crop,))
+        if factor_crops not in ('random', 'grid'):
+            raise ValueError("factor_crops must be 'random' or 'grid', got %r" % (factor_crops,))
         Trainer.__init__(self)
+        self.crop = crop
+        self.crop_seed = int(crop_seed)
+        self.factor_crops = factor_crops
         self.feature_dim = feature_dim
         self.conv_hidden = conv_hidden
         self.batch_size = batch_size
@@ -167,6 +181,7 @@ class DCUE(Trainer):
         self.device = torch.device(device if device is not None else "cuda")
         self.defer_embedding = defer_embedding
         self._tracks = None       # [n_items][131][128] HBM table, item-index order
+        self._store = None        # crop='epoch': (data [total_frames][128], frame_ptr [n_items + 1]) beside it
         self._item_meta = None    # metadata index of every item index
         self._plan = None
         self._plan_n = None
@@ -214,11 +229,34 @@ class DCUE(Trainer):
         if self._tracks is not None and self._tracks_src is item_dataset:
             return
         meta = item_dataset.item_rows()
-        table_meta = item_dataset.track_table(self.device, n_meta=max(len(item_dataset.songid2metaindex), 1))
-        rows = torch.from_numpy(np.where(meta >= 0, meta, 0)).to(self.device)
-        self._tracks = table_meta.index_select(0, rows).contiguous()
+        if self.crop == 'epoch':
+            data, frame_ptr = item_dataset.track_store(self.device)
+            self._store = (data, frame_ptr)
+            self._tracks = torch.empty((len(meta), nat.N_FRAMES, nat.N_MELS), dtype=data.dtype, device=self.device)
+            self._plan = None  # a plan binds the table's address
+            bad = int(self._recrop().count_nonzero())
+            if bad:
+                raise RuntimeError("track store: %d tracks with an extent outside the store" % bad)
+        else:
+            table_meta = item_dataset.track_table(self.device, n_meta=max(len(item_dataset.songid2metaindex), 1))
+            rows = torch.from_numpy(np.where(meta >= 0, meta, 0)).to(self.device)
+            self._tracks = table_meta.index_select(0, rows).contiguous()
+            self._store = None
         self._item_meta = meta
         self._tracks_src = item_dataset
+
+    def _recrop(self, draw=None):
+        """crop='epoch': cut the whole track table again, in place, into the buffer the plan is bound
+        to -- a random window of every track from (crop_seed, draw), draw = nn_epoch by default, the
+        same on every rank. Returns the call's flags (device). Only at an epoch boundary: the plan must
+        hold no lookahead (it would feed the next step statistics of the old rows), and this stream
+        first waits for what the last step left on the plan's side streams, which read the table."""
+        data, frame_ptr = self._store
+        if self._plan is not None:
+            self._plan.require_no_lookahead()
+            self._plan.sync(nat.stream_handle(self.device))
+        cfg = nat.crop_config(nat.CROP_RANDOM, seed=self.crop_seed, draw=self.nn_epoch if draw is None else draw)
+        return nat.crop_tracks(data, frame_ptr, cfg, self._tracks)
 
     def _n_neg(self, ds):
         """Negatives per row: the dataset's neg_samples, as in the reference, where the trainer's
@@ -246,6 +284,10 @@ class DCUE(Trainer):
         neg = self._negatives(ds)
         B, N = self.batch_size, self._n_neg(ds)
         plan = self._train_plan(N)
+        if self._store is not None:
+            # before the sampling stream joins the main one below: every later reader of the table --
+            # the steps and the lookaheads they start -- is ordered after this stream's re-crop
+            self._recrop()
         users_all, items_all = self._rows(ds)
         batches = list(loader)  # the loader's RNG draws happen when its iteration starts, as before
         dev = self.device
@@ -434,7 +476,9 @@ class DCUE(Trainer):
         n_meta = len(item_data.songid2metaindex)
         out = torch.zeros([n_meta, self.feature_dim], device=self.device)
         items = np.nonzero(self._item_meta >= 0)[0].astype(np.int32)
-        if len(items):
+        if len(items) and self._store is not None:
+            self._factors_cropped(items, int(n_iter), out)
+        elif len(items):
             step = 8192
             ds = nat.storage_dims(self.model._flat["dims"]).feature_dim
             feat = torch.empty((min(step, len(items)), ds), device=self.device)
@@ -453,6 +497,43 @@ class DCUE(Trainer):
             nat.check(nat.lib().dcue_factor_repeat_mean(nat.ptr(out), out.numel(), int(n_iter), nat.stream_handle()),
                       "dcue_factor_repeat_mean")
         return out
+
+    def _factor_crop(self, j, n_iter):
+        """Window j of the n_iter an item factor averages over: 'random' draws 2^32 + j -- apart from
+        every epoch's draw and the same each time, so factors stay comparable across epochs --, 'grid'
+        the j-th of n_iter evenly spread windows."""
+        if self.factor_crops == 'grid':
+            return nat.crop_config(nat.CROP_GRID, grid_j=j, grid_n=n_iter)
+        return nat.crop_config(nat.CROP_RANDOM, seed=self.crop_seed, draw=nat.CROP_FACTOR_DRAW0 + j)
+
+    def _factors_cropped(self, items, n_iter, out):
+        """nn/dcue.py:655-668 with a store bound: n_iter real passes. Per chunk of 8,192 items each
+        pass cuts its windows into a scratch table through `rows` (the training table is never
+        touched), runs the eval tower over it and adds the result in fp32, in pass order; one divide
+        at the end -- the reference's `+=` then `/=`."""
+        data, frame_ptr = self._store
+        step = min(8192, len(items))
+        ds = nat.storage_dims(self.model._flat["dims"]).feature_dim
+        scratch = torch.empty((step, nat.N_FRAMES, nat.N_MELS), dtype=data.dtype, device=self.device)
+        feat = torch.empty((step, ds), device=self.device)
+        acc = torch.empty((step, self.feature_dim), device=self.device)
+        ident = torch.arange(step, dtype=torch.int32, device=self.device)
+        div = torch.tensor(float(n_iter), device=self.device)  # a device operand: a true fp32 division
+        model = self.model._model_struct()
+        for s in range(0, len(items), step):
+            it = torch.from_numpy(items[s:s + step]).to(self.device)
+            n = it.numel()
+            tr = nat.Tracks(scratch.data_ptr(), n, 0 if scratch.dtype == torch.float16 else 1, 0)
+            ws = self._factor_ws(1, n)
+            acc.zero_()
+            for j in range(n_iter):
+                nat.crop_tracks(data, frame_ptr, self._factor_crop(j, n_iter), scratch[:n], rows=it)
+                nat.check(nat.lib().dcue_item_tower_eval(ctypes.byref(model), ctypes.byref(tr), nat.ptr(ident), n,
+                                                         nat.ptr(ws), ws.numel(), nat.ptr(feat), nat.stream_handle()),
+                          "dcue_item_tower_eval")
+                acc[:n] += feat[:n, :self.feature_dim]
+            rows = torch.from_numpy(self._item_meta[items[s:s + step]]).to(self.device)
+            out.index_copy_(0, rows, acc[:n] / div)
 
     def _item_feat_by_index(self):
         """item factors in item-index order (the evaluator's candidate rows)."""
@@ -594,13 +675,19 @@ class DCUE(Trainer):
         return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
 
     # ------------------------------------------------------------------ unseen songs
-    def embed_audio(self, wave, logmel=None, frame0=0):
+    def embed_audio(self, wave, logmel=None, frame0=0, crops=None):
         """[n, d] item factors of waveforms ([n_samples] or [n, n_samples], mono, at the front end's
         sample rate) -- the cold-start step for a song nobody has played: audio.LogMel.track_rows writes
         a temporary fp16 track table on the GPU (frames frame0 .. frame0 + 130 of each clip) and
         dcue_item_tower_eval reads it where it lies. Needs no dataset and no host copy. logmel: an
         audio.LogMel (default: one with the default configuration, kept for later calls). A clip with a
-        NaN or infinite sample raises ValueError naming it."""
+        NaN or infinite sample raises ValueError naming it.
+
+        crops=n embeds the whole clip instead of one window: the front end runs over every frame, the
+        rows become a uniform track store, and the factor is the fp32 mean, in window order, of the
+        tower over n evenly spread 131-frame windows (dcue_crop_tracks, DCUE_CROP_GRID: the first starts
+        at frame 0, the last ends at the clip's last frame; n = 1 is the centre window). A clip shorter
+        than 131 frames raises ValueError, as a frame0 past the end does."""
         from dcrecommend import audio
         if self.model._flat["dims"].tower == nat.TOWERS[nat.TEXT_TOWER]:
             raise RuntimeError("embed_audio: the text tower needs a song's tokens too; audio alone is not enough")
@@ -610,36 +697,58 @@ class DCUE(Trainer):
             logmel = self._logmel
         self.model.eval()
         self.model._require_device()
-        table = logmel.track_rows(wave, frame0, torch.float16)
-        n = int(table.shape[0])
         ds = nat.storage_dims(self.model._flat["dims"]).feature_dim
+        if crops is None:
+            return self._tower_over(logmel.track_rows(wave, frame0, torch.float16), ds)[:, :self.feature_dim].contiguous()
+        crops = int(crops)
+        if crops < 1 or frame0 != 0:
+            raise ValueError("embed_audio: crops must be >= 1 and goes without frame0")
+        rows = logmel.transform(wave, 0, None, torch.float16)  # every frame of every clip
+        n, T = int(rows.shape[0]), int(rows.shape[1])
+        if T < nat.N_FRAMES:
+            raise ValueError("embed_audio: crops needs clips of at least %d frames; the frame range of these "
+                             "clips ends at %d (no silent padding)" % (nat.N_FRAMES, T))
+        acc = torch.zeros((n, self.feature_dim), device=self.device)
+        if n:
+            frame_ptr = torch.arange(n + 1, dtype=torch.int64, device=self.device) * T
+            table = torch.empty((n, nat.N_FRAMES, nat.N_MELS), dtype=torch.float16, device=self.device)
+            for j in range(crops):
+                nat.crop_tracks(rows.view(n * T, nat.N_MELS), frame_ptr,
+                                nat.crop_config(nat.CROP_GRID, grid_j=j, grid_n=crops), table)
+                acc += self._tower_over(table, ds)[:, :self.feature_dim]
+        return acc / torch.tensor(float(crops), device=self.device)
+
+    def _tower_over(self, table, ds):
+        """dcue_item_tower_eval over every row of a temporary track table: [n, d_s] features."""
+        n = int(table.shape[0])
         feat = torch.empty((max(n, 1), ds), device=self.device)
         if n:
-            tr = nat.Tracks(table.data_ptr(), n, 0, 0)
+            tr = nat.Tracks(table.data_ptr(), n, 0 if table.dtype == torch.float16 else 1, 0)
             it = torch.arange(n, dtype=torch.int32, device=self.device)
             model = self.model._model_struct()
             ws = self._factor_ws(1, n)
             nat.check(nat.lib().dcue_item_tower_eval(ctypes.byref(model), ctypes.byref(tr), nat.ptr(it), n,
                                                      nat.ptr(ws), ws.numel(), nat.ptr(feat), nat.stream_handle()),
                       "dcue_item_tower_eval")
-        return feat[:n, :self.feature_dim].contiguous()
+        return feat[:n]
 
-    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None):
+    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None, crops=None):
         """The k catalogue songs nearest to each clip, by the cosine of its embed_audio factor to the
         item factors: one list of (song_id, score) pairs per clip, as similar_songs returns (nothing is
-        excluded: the clip is not in the catalogue)."""
+        excluded: the clip is not in the catalogue). crops: as embed_audio -- the whole song, not its
+        first window."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
-        q = self.embed_audio(wave, logmel)
+        q = self.embed_audio(wave, logmel, crops=crops)
         out = self._topk("audio", ds, False).topk(q, self._item_feat_by_index(), np.arange(q.shape[0]), k)
         return self._as_pairs(ds, *out)
 
-    def listeners_for_audio(self, wave, k=10, logmel=None):
+    def listeners_for_audio(self, wave, k=10, logmel=None, crops=None):
         """The k users with the highest cosine to each clip -- "who should hear this": the clips'
         embed_audio factors against user_factors on the same kernel. One list of (user_id, score) pairs
-        per clip, best first."""
+        per clip, best first. crops: as embed_audio."""
         self._require_factors()
-        q = self.embed_audio(wave, logmel)
+        q = self.embed_audio(wave, logmel, crops=crops)
         key = ("topk", "listeners")
         if key not in self._evals:
             self._evals[key] = rank.TopK(None, None, None, self.device, n_cand=int(self.user_factors.shape[0]))
@@ -834,7 +943,7 @@ class DCUE(Trainer):
                 "lr", "beta_one", "beta_two", "eps", "weight_decay", "restart_period", "t_mult", "num_epochs",
                 "model_type", "eval_pct", "val_pct", "n_users", "n_items", "epoch_size", "nn_epoch",
                 "best_val_map", "best_val_auc", "best_val_loss", "metadata_path", "triplets_path", "model_dir",
-                "defer_embedding")
+                "defer_embedding", "crop", "crop_seed", "factor_crops")
     _TENSORS = ("item_factors", "user_factors", "best_item_factors", "best_user_factors")
 
     def _checkpoint(self):
@@ -866,6 +975,8 @@ class DCUE(Trainer):
         for k in self._SCALARS:
             if k in ck:
                 setattr(self, k, ck[k])
+        if "crop" not in ck:  # a checkpoint from before the per-epoch crops: the table cut once, at load
+            self.crop, self.crop_seed, self.factor_crops = 'load', 0, 'random'
         self._init_nn()
         self.model.load_state_dict(ck["model"])
         for k in self._TENSORS:

@@ -575,7 +575,10 @@ int dcue_rank_metrics(const float* query_feat, int64_t n_query_rows, const float
                       int32_t mode, int32_t query_batch, void* ws, size_t ws_bytes, double* auc,
                       double* ap, int32_t* has_pos, void* stream);
 /* DCUE._item_factors' averaging (nn/dcue.py:655-668): f <- (f + f + ... n_iter times) / n_iter in
- * fp32, for 131-frame tracks whose n_iter eval passes are identical (no random crop). */
+ * fp32. It stands for the n_iter eval passes only where they are identical: a catalogue without a
+ * full-length store (the table was cropped once, at load), or one whose tracks all have at most 131
+ * frames. With a store bound the trainer runs n_iter real passes over dcue_crop_tracks windows and
+ * accumulates them itself (DCUE._factors_over). */
 int dcue_factor_repeat_mean(float* f, int64_t n, int32_t n_iter, void* stream);
 
 /* ------------------------------------------------------------------- top-K recommendation (ABI 17) */
@@ -900,6 +903,77 @@ int dcue_logmel_table_fill_host(const dcue_logmel_config* cfg, void* table_host,
 int dcue_logmel_table_init(const dcue_logmel_config* cfg, void* table_dev, size_t bytes, void* stream);
 int dcue_logmel(const dcue_logmel_config* cfg, const void* table_dev, const float* wave, int64_t n_clips,
                 int64_t n_samples, int64_t frame0, int32_t n_frames, void* out, int32_t* flags, void* stream);
+
+/* ----------------------------------- window crops of full-length tracks (added under ABI 17) */
+/* The reference trains on a different DCUE_N_FRAMES-frame window of a song every time it loads the song
+ * (DCUEDataset._sample, datasets/dcuedataset.py:166-187: X[:, s:s+131], s = randint(0, T - 131)) and
+ * averages its item factors over ten such windows (nn/dcue.py:655-668). dcue_crop_tracks cuts a track
+ * table out of full-length tracks kept in HBM, one window per track, by a rule that is a function of
+ * (configuration, track index, track length) alone -- not of the output row, the launch or the batch.
+ * Store. dcue_track_store: data [total_frames][DCUE_N_MELS], frame-major, fp16 or fp32 -- dcue_tracks'
+ *   row layout without the fixed 131 -- and frame_ptr, device int64 [n_tracks + 1]: track t holds frames
+ *   frame_ptr[t] .. frame_ptr[t+1] - 1. A track may have length 0 (a song without audio).
+ * Output. Row i of out [n_out][131][128] (out_dtype as dcue_tracks.dtype; `out` is a dcue_tracks table as it
+ *   stands) is the window of track rows[i] (int32, device), or of track i when rows == NULL. Repeats are
+ *   allowed. starts (int32 [n_out], device, nullable) receives the window's first frame inside its track;
+ *   flags (int32 [n_out], device) is written for every row: 0, or the bits below.
+ * Window rule. L = frame_ptr[t+1] - frame_ptr[t], W = 131, all in 64-bit integers:
+ *   L <= W            start 0: the L frames are copied and the other W - L rows are zero (the reference
+ *                     pads at the end, F.pad(X, (0, W - L))), whatever the mode.
+ *   DCUE_CROP_FIRST   start 0.
+ *   DCUE_CROP_CENTER  start (L - W) / 2.
+ *   DCUE_CROP_GRID    window grid_j of grid_n evenly spread ones: start grid_j * (L - W) / (grid_n - 1);
+ *                     grid_n == 1 is CENTER; grid_j = grid_n - 1 is the last window, start L - W.
+ *   DCUE_CROP_RANDOM  start = mulhi64(h, L - W) = floor(h * (L - W) / 2^64), uniform over [0, L - W).
+ *                     This is the reference's np.random.randint(0, L - W), whose high end is exclusive: the
+ *                     last window (start L - W) is never drawn, and L = W + 1 always gives start 0. That
+ *                     is kept. With mix the splitmix64 finaliser of dcue_user_foldin (z ^= z >> 30;
+ *                     z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31) and
+ *                     G = 0x9E3779B97F4A7C15, all modulo 2^64:
+ *                       z0 = mix(seed + G * (t + 1)),  h = mix(z0 + G * (draw + 1)),
+ *                     t the track's index in the store. `draw` is the caller's counter (the trainer passes
+ *                     its epoch): the same (seed, draw) gives the same table on every rank and in every
+ *                     launch; another draw gives every track another, independent window.
+ * Conversions. fp16 -> fp32 is exact; fp32 -> fp16 rounds to nearest even, as dcue_logmel does.
+ * Guards on the device (frame_ptr and rows are device memory): a row whose extent is negative
+ *   (frame_ptr[t] < 0 or frame_ptr[t+1] < frame_ptr[t]) or reaches past total_frames sets
+ *   DCUE_CROP_FLAG_BAD_EXTENT; a row whose rows[i] (or i, without rows) lies outside [0, n_tracks) sets
+ *   DCUE_CROP_FLAG_BAD_ROW. Such a row is written as zeros with start 0; nothing is read or written out
+ *   of bounds and the other rows are unaffected, bit for bit.
+ * Refused on the host before any device call, each with a dcue_last_error text (DCUE_ERR_INVALID): a
+ *   null store, cfg, out or flags; a negative n_tracks, total_frames or n_out; an unknown mode or dtype;
+ *   grid_n < 1, grid_j < 0 or grid_j >= grid_n (GRID); with n_out > 0 a null frame_ptr or data, data or
+ *   out not 16-byte aligned, out overlapping the store's data. DCUE_ERR_UNSUPPORTED: total_frames beyond
+ *   INT32_MAX (starts are int32). n_out == 0 is DCUE_OK. One launch, no workspace, no LDS; asynchronous
+ *   on `stream`.
+ * dcue_crop_starts_host: the same arithmetic on the CPU (no device call): starts_host[i] for a track of
+ *   lengths_host[i] frames at store index track_ids_host[i] (null: i). For tests, and for callers that
+ *   need the windows without reading them back. */
+#define DCUE_CROP_FIRST 0
+#define DCUE_CROP_CENTER 1
+#define DCUE_CROP_GRID 2
+#define DCUE_CROP_RANDOM 3
+#define DCUE_CROP_FLAG_BAD_EXTENT 1
+#define DCUE_CROP_FLAG_BAD_ROW 2
+typedef struct dcue_track_store {
+  const void* data;         /* [total_frames][128] */
+  const int64_t* frame_ptr; /* [n_tracks + 1], device */
+  int64_t n_tracks;
+  int64_t total_frames;
+  int32_t dtype;            /* 0 = fp16, 1 = fp32 */
+  int32_t reserved;
+} dcue_track_store;
+typedef struct dcue_crop_config {
+  int32_t mode;             /* DCUE_CROP_* */
+  int32_t grid_j, grid_n;   /* DCUE_CROP_GRID */
+  int32_t reserved;
+  uint64_t seed, draw;      /* DCUE_CROP_RANDOM */
+} dcue_crop_config;
+int dcue_crop_tracks(const dcue_track_store* store, const dcue_crop_config* cfg, const int32_t* rows,
+                     int64_t n_out, void* out, int32_t out_dtype, int32_t* starts, int32_t* flags,
+                     void* stream);
+int dcue_crop_starts_host(const dcue_crop_config* cfg, const int64_t* lengths_host,
+                          const int64_t* track_ids_host, int64_t n, int64_t* starts_host);
 
 #ifdef __cplusplus
 }

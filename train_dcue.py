@@ -78,6 +78,13 @@ def parse(argv=None):
                     help="--eval-k also reports ild@K, the lists' mean intra-list diversity")
     ap.add_argument("--eval-diversity", type=float, metavar="L",
                     help="--eval-k scores the MMR re-ranked lists (lambda = L) instead of the plain ranking")
+    ap.add_argument("--crop", choices=["load", "epoch"], default="load",
+                    help="DCUE(crop=...): 'load' cuts each track's 131-frame window once, when the catalogue is "
+                         "loaded; 'epoch' keeps the full-length tracks in HBM and cuts a fresh random window of "
+                         "every track before each training sub-epoch (dcue_crop_tracks)")
+    ap.add_argument("--crop-seed", type=int, default=0, help="DCUE(crop_seed=...): the seed of --crop epoch's windows")
+    ap.add_argument("--factor-crops", choices=["random", "grid"], default="random",
+                    help="DCUE(factor_crops=...), with --crop epoch: the windows the item factors average over")
     args = ap.parse_args(argv)
     if bool(args.eval_k) != bool(args.eval_out):
         ap.error("--eval-k and --eval-out go together")
@@ -154,7 +161,8 @@ def main(argv=None):
     dcue = DCUE(feature_dim=args.feature_dim, conv_hidden=args.conv_hidden, batch_size=args.batch_size,
                 neg_batch_size=args.neg_batch_size, u_embdim=args.u_embdim, margin=args.margin, lr=args.lr,
                 weight_decay=args.weight_decay, num_epochs=args.num_epochs, eval_pct=args.eval_pct,
-                val_pct=args.val_pct, optimize=args.optimize, model_type=args.model_type)
+                val_pct=args.val_pct, optimize=args.optimize, model_type=args.model_type, crop=args.crop,
+                crop_seed=args.crop_seed, factor_crops=args.factor_crops)
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
     if args.recommend_k > 0 and args.recommend_out:
