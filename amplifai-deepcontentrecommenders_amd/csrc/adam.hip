@@ -80,7 +80,7 @@ struct PackArgs {
 __global__ __launch_bounds__(256) void k_adam_dense_pack(float* __restrict__ p, float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v,
                                                          long lo, long n, AdamScalars s, PackArgs pa,
-                                                         float* __restrict__ wpack, float gdiv, unsigned* sig) {
+                                                         float* __restrict__ wpack, float gdiv) {
   const long n4 = n / 4;
   for (long i = lo / 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
@@ -114,7 +114,6 @@ __global__ __launch_bounds__(256) void k_adam_dense_pack(float* __restrict__ p, 
     if (gdiv > 0.f) g[i] = gi = __fdiv_rn(gi, gdiv);
     adam_elem(p[i], gi, m[i], v[i], s);
   }
-  dev_signal_wg(sig);  // (plans: the late segments' Adam, for the next step's conv 2)
 }
 
 // User table: one wave per row; rows without a gradient this step get g = 0 (the reference's dense
@@ -382,10 +381,9 @@ int frz_before_record(const dcue_model* md, const AdamScalars& sc, int t, hipStr
 // current, so every row is replayed at least once per `cap` steps -- the replay work spread evenly
 // over the steps (it runs on the user-tower stream, beside the item tower) instead of a full-table
 // sweep every cap steps. A workgroup owns whole rows: it reads their clocks, replays, then sets them.
-// Round 6: the grid strides over groups of rows_per_block rows, so DCUE_SLICE_WGS can bound it (A/B
-// diagnostic for the steady-state tax). Bounds of 64-512 workgroups made the slice
-// slower without shortening the critical path, so the default stays one workgroup
-// per group; a workgroup stages the window's history and replay bound once for all its groups.
+// The grid strides over groups of rows_per_block rows; bounds of 64-512 workgroups made the slice
+// slower without shortening the critical path, so the launch gives every
+// group a workgroup of its own; a workgroup stages the window's history and replay bound once.
 __global__ __launch_bounds__(256) void k_emb_flush_rows(float* __restrict__ p, float* __restrict__ m,
                                                         float* __restrict__ v, const dcue_emb_log* hdr,
                                                         int32_t* emb_step, long r0, long r1, int E,
@@ -487,13 +485,7 @@ int launch_emb_flush_rows(const dcue_model* md, int step, hipStream_t s) {
   int rpb = 4096 / E;  // rows per group: ~4 K elements (1 K float4) per pass of 256 threads
   if (rpb < 1) rpb = 1;
   if (rpb > 256) rpb = 256;
-  static const long max_wgs = [] {
-    const char* e = getenv("DCUE_SLICE_WGS");
-    const long v = e ? atol(e) : 1L << 30;
-    return v < 1 ? 1L : v;
-  }();
-  long blocks = (r1 - r0 + rpb - 1) / rpb;
-  if (blocks > max_wgs) blocks = max_wgs;
+  const long blocks = (r1 - r0 + rpb - 1) / rpb;
   TimerScope tsc;
   int st = timer_begin(&tsc, DCUE_TIMED_EMB_SLICE, s);
   if (st) return st;
@@ -879,21 +871,19 @@ int launch_bn0_grads_adam(const float* G, const float* E, const float* gamma0, c
   return DCUE_OK;
 }
 
-long adam_dense_blocks(long len) { return len >= 512L * 1024 ? 512 : (len / 4 + 255) / 256 + 1; }
-
 int launch_adam(const dcue_model* md, const dcue_adam_args* a, const int64_t* poff, hipStream_t s,
-                bool flush_slice, long dense_lo, long dense_hi, bool defer_dgrad2, unsigned* sig) {
+                bool flush_slice, long dense_lo, long dense_hi, bool defer_dgrad2) {
   const AdamScalars sc = form_scalars(a);
   const float gdiv = a->grad_div > 1.0 ? (float)a->grad_div : 0.f;
   const int parts = a->parts ? a->parts : (DCUE_ADAM_DENSE | DCUE_ADAM_EMBEDDING);
   const long n = dense_hi >= 0 ? dense_hi : poff[DCUE_N_DENSE_SEGMENTS];
   if (parts & DCUE_ADAM_DENSE) {  // Adam + the conv-weight repack in one sweep
     const long len = n - dense_lo;
-    const long blocks = adam_dense_blocks(len);
+    const long blocks = len >= 512L * 1024 ? 512 : (len / 4 + 255) / 256 + 1;
     PackArgs pa = pack_args(md, poff);
     if (defer_dgrad2) pa.seg[1].bwd = pa.seg[1].f16b = -1;  // (the next forward of conv 2 writes them)
     DCUE_LAUNCH(k_adam_dense_pack, dim3((unsigned)blocks), dim3(256), 0, s, md->params, md->grads, md->exp_avg,
-                       md->exp_avg_sq, dense_lo, n, sc, pa, md->wpack, gdiv, sig);
+                       md->exp_avg_sq, dense_lo, n, sc, pa, md->wpack, gdiv);
     DCUE_LAUNCH_CHECK();
   }
   if ((parts & DCUE_ADAM_EMBEDDING) && md->emb_step) {

@@ -22,14 +22,7 @@ namespace dcue {
 // (alternating between two streams, each with its own partial-sum buffers). Forks and joins are
 // event-ordered against the caller's stream, so the calls stay stream-ordered (and capturable).
 
-unsigned sync_event_flags() {
-  static const unsigned f = [] {
-    const char* e = getenv("DCUE_EVENT_SCOPE");
-    return (e && e[0] == 's') ? (unsigned)hipEventDisableTiming
-                              : (unsigned)(hipEventDisableTiming | hipEventReleaseToDevice);
-  }();
-  return f;
-}
+unsigned sync_event_flags() { return hipEventDisableTiming | hipEventReleaseToDevice; }
 
 SidePool* side_pool() {
   static SidePool pools[64];
@@ -37,28 +30,8 @@ SidePool* side_pool() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   SidePool& p = pools[dev];
   if (!p.st[0]) {
-    // DCUE_SIDE_PRIO=low: the side streams at the device's least stream priority, so the command
-    // processor favours the caller's (critical-path) queue when both have workgroups to dispatch
-    static const bool low = [] {
-      const char* e = getenv("DCUE_SIDE_PRIO");
-      return e && e[0] == 'l';
-    }();
-    // DCUE_USER_PRIO=high: the user stream (st[0]) at the device's greatest priority, so its short
-    // user-tower GEMMs are dispatched between the item tower's conv workgroups (A/B knob)
-    static const bool user_high = [] {
-      const char* e = getenv("DCUE_USER_PRIO");
-      return e && e[0] == 'h';
-    }();
-    int least = 0, greatest = 0;
-    if ((low || user_high) && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return nullptr;
-    for (int i = 0; i < 3; ++i) {
-      hipStream_t& s = p.st[i];
-      const bool prio = low || (user_high && i == 0);
-      const int pr = (user_high && i == 0) ? greatest : least;
-      if ((prio ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, pr)
-                : hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess)
-        return nullptr;
-    }
+    for (int i = 0; i < 3; ++i)
+      if (hipStreamCreateWithFlags(&p.st[i], hipStreamNonBlocking) != hipSuccess) return nullptr;
     for (auto& e : p.ev)
       if (hipEventCreateWithFlags(&e, sync_event_flags()) != hipSuccess) return nullptr;
   }
@@ -255,7 +228,7 @@ struct Ws {
   float *du, *dfcopy, *df;
   float* g[6];
   float *dh1, *de;
-  float *wpart[3], *bpart[3], *G, *S;  // wgrad partials: one set per wgrad stream
+  float *wpart, *bpart, *G, *S;  // the conv-1 weight gradient's split-K partials, its reduce's outputs
   float *wpm[5], *bpm[5];                // k_conv_wgrad_multi's partials, layers 2..5 and the fc
   float* xhat0;          // [M][kXp][128] bn0-normalised, zero-padded input: conv-1 wgrad's X operand
   float* dx1;            // [M][33][H] BN1 backward at the pooled positions: conv-1 wgrad's dz operand
@@ -337,18 +310,9 @@ size_t carve(const dcue_dims* d, int B, int N, int M, void* base, Ws* w) {
   for (int l = 1; l <= 5; ++l) w->g[l] = ar.take<float>((long)M * layer_geom(l).lp * (l == 5 ? D : H));
   w->dh1 = ar.take<float>((long)B * E);
   w->de = ar.take<float>((long)B * E);
-  long wp = 0, bp = 0;
-  for (int l = 1; l <= 5; ++l) {
-    const int cin = l == 1 ? kMels : H, cout = l == 5 ? D : H;
-    const long nch = wgrad_nchunk(l, M, cout, cin, true);  // (so the size never falls as M grows)
-    const long e = nch * cout * cin * layer_geom(l).ks;
-    if (e > wp) wp = e;
-    if (nch * 5 * cout > bp) bp = nch * 5 * cout;
-  }
-  for (int i = 0; i < 3; ++i) {
-    w->wpart[i] = ar.take<float>(wp);
-    w->bpart[i] = ar.take<float>(bp);
-  }
+  const long nch1 = wgrad_nchunk(1, M, H, kMels, true);  // (so the size never falls as M grows)
+  w->wpart = ar.take<float>(nch1 * H * kMels * layer_geom(1).ks);
+  w->bpart = ar.take<float>(nch1 * 5 * H);
   for (int l = 2; l <= 6; ++l) {  // 6: the fc layer (a 1x1 conv over bn5(y5), D -> D)
     const int cin = l == 6 ? D : H, cout = l >= 5 ? D : H;
     const long nch = wgrad_nchunk(l, M, cout, cin, true);  // (so the size never falls as M grows)
@@ -461,26 +425,6 @@ TextBranch text_branch_ws(const Ctx& c, const dcue_tracks* t, const Ws& w) {
   tb.ticket = w.tticket;
   tb.part = w.tpart;
   return tb;
-}
-
-// DCUE_SLICE_STREAM: the side stream of the rolling flush slice (0: the user stream; w0 / w1: the
-// weight-gradient streams st[1] / st[2])
-int slice_stream() {
-  static const int v = [] {
-    const char* e = getenv("DCUE_SLICE_STREAM");
-    return !e ? 0 : (e[0] == 'w' && e[1] == '0') ? 1 : (e[0] == 'w' && e[1] == '1') ? 2 : 0;
-  }();
-  return v;
-}
-
-// DCUE_TEXT_SIDE=0: the training forward's text branch on the caller's stream after conv 5 instead
-// of on the user stream beside the audio convs (A/B)
-bool text_side_on() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_TEXT_SIDE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 // Item tower forward. train: batch statistics (weighted by counts, accumulated exactly by the
@@ -755,7 +699,7 @@ int dcue_debug_launch_shape(const dcue_dims* dims, int32_t layout, int32_t B, in
       o[1] = o[2] = o[3] = 0;
       continue;
     }
-    wgrad_shape(l, M, l >= 5 ? D : H, l == 1 ? kMels : l == 6 ? D : H, SRC_TRACK_F16, l <= 2, o);
+    wgrad_shape(l, M, l >= 5 ? D : H, l == 1 ? kMels : l == 6 ? D : H, l <= 2, o);
   }
   tail_shape(N, M, D, gather, gather && M <= kCopyListMaxItems, fc, o);
   return DCUE_OK;
@@ -878,7 +822,7 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   if (!o.prologue_done) TRY(batch_counts(b, w, s));
   HPROF("capi:4");
   hipEvent_t ev_uf = nullptr, ev_tx = nullptr;
-  const bool text_side = c.text && text_side_on();
+  const bool text_side = c.text;  // the text branch runs on a side stream beside the audio convs
   // plans: the score kernel waits for the user tower on the device (DevWait), not by a stream wait
   const bool uf_sig = o.sig != nullptr && !capturing_step();
   static const bool split_fwd = [] {  // DCUE_USER_FWD=split: k_emb_sync + two k_tgemm (A/B)
@@ -956,34 +900,9 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
       }
       TRY(timer_end(&tsc));
     }
-    static const bool skip_slice = [] {  // DCUE_SLICE_SKIP=1: timing diagnostic only (wrong table)
-      const char* e = getenv("DCUE_SLICE_SKIP");
-      return e && e[0] == '1';
-    }();
-    if (o.flush_slice_step >= 0 && m->emb_step && !skip_slice) {
-      // DCUE_SLICE_STREAM=w1 / w0: the slice on a weight-gradient stream, after this user tower (its
-      // rows' claims) and before the step's user-table Adam (which waits for *slice_done): a long
-      // slice then holds no user-stream work behind it (A/B)
-      const int ss = slice_stream();
-      if (ss > 0 && o.slice_done) {
-        hipEvent_t e_u = nullptr;
-        TRY(fork_point(sp, su, &e_u));
-        TRY(wait_point(sp->st[ss], e_u));
-        ForkAfter fk(sp, sp->st[ss], o.slice_done);
-        TRY(launch_emb_flush_rows(m, o.flush_slice_step, sp->st[ss]));
-        TRY(fk.done());
-      } else {
-        TRY(launch_emb_flush_rows(m, o.flush_slice_step, su));
-      }
-    }
+    if (o.flush_slice_step >= 0 && m->emb_step) TRY(launch_emb_flush_rows(m, o.flush_slice_step, su));
     return DCUE_OK;
   };
-  // DCUE_USER_EARLY=1: the user tower is issued right after conv 1 instead of after the whole item
-  // tower, so the host's issue order does not hold it behind four conv launches (A/B knob)
-  static const bool early = [] {
-    const char* e = getenv("DCUE_USER_EARLY");
-    return e && e[0] == '1';
-  }();
   // with the side-issue thread (side.hip) the user tower is issued there, beside the item tower's issue
   SideQueue side;
   int ust = DCUE_OK;
@@ -1000,21 +919,20 @@ int forward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t,
   if (late_first) TRY(wait_point(s, o.wait_late));
   // the fc waits for the text branch: its launch issued (the side thread's part done), then its end
   const std::function<int()> text_join = [&]() -> int {
-    if (!early && !side.threaded()) TRY(user_part());
+    if (!side.threaded()) TRY(user_part());
     TRY(side.wait(useq));
     return wait_point(s, ev_tx);
   };
-  bool user_done = false;
-  if (text_side) user_done = !early || side.threaded();  // (text_join issues the user part)
+  const bool user_done = text_side;  // (text_join issues the user part)
   // conv 2's wait for the previous step's late Adam: on the device when the plan signals it
   const bool l2_dev = o.late_wait.flag != nullptr && !late_first && !capturing_step();
   TRY(item_forward(c, w, t, b->item_track, b->n_items, copies, train != 0, w.counts, nullptr, s,
                    o.prologue_done, o.input_stats_done && o.prologue_done, o.clear_bn0,
                    late_first || l2_dev ? nullptr : o.wait_late,
-                   post_after_l1 ? &post_user : early && !side.threaded() ? &user_part : nullptr, o.sync_bn,
+                   post_after_l1 ? &post_user : nullptr, o.sync_bn,
                    text_side ? &text_join : nullptr, l2_dev ? &o.late_wait : nullptr,
                    start_dev ? const_cast<unsigned*>(o.start_wait.flag) : nullptr));
-  if (!early && !side.threaded() && !user_done) TRY(user_part());
+  if (!side.threaded() && !user_done) TRY(user_part());
   TRY(side.wait(useq));
   if (!uf_sig) TRY(wait_point(s, ev_uf));
   HPROF("capi:9");
@@ -1104,33 +1022,6 @@ bool late_wait_at_conv1() {
   return on;
 }
 
-// DCUE_LATE_JOIN=hop: split plans keep the join through wgrad stream 0 (A/B, backward_impl)
-static bool late_join_hop() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_LATE_JOIN");
-    return e && e[0] == 'h';
-  }();
-  return on;
-}
-
-static bool fuse_late_adam_on() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_FUSE_LATE_ADAM");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// DCUE_FORK_ONCE=1: one fork point on the dgrad chain (after dgrad 3) for both weight-gradient
-// launches instead of two (A/B diagnostic: each launch-bound event costs the chain a gap)
-static bool fork_once() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_FORK_ONCE");
-    return e && e[0] == '1';
-  }();
-  return on;
-}
-
 int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t, void* ws, size_t ws_bytes,
                   const float* dscores, float emb_grad_scale, const StepOpts& o, hipStream_t s) {
   Ctx c;
@@ -1186,9 +1077,9 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   hipEvent_t ev_x0 = nullptr;
   const bool f16w = wgrad_f16_on();  // split-f16 weight gradients (conv_wgrad.hip)
   // split plans: Adam over bn0 / conv 1 / bn1 rides in the bn0-gradient launch (adam.hip
-  // k_bn0_grads_adam) instead of a launch of its own behind it (DCUE_FUSE_LATE_ADAM=0: separate);
-  // not under an exchange, whose Adam must wait for the all-reduced gradient
-  const bool fuse_late = o.dense_split && !o.comm && o.dense_split->grad_div <= 1.0 && fuse_late_adam_on();
+  // k_bn0_grads_adam) instead of a launch of its own behind it; not under an exchange, whose Adam
+  // must wait for the all-reduced gradient
+  const bool fuse_late = o.dense_split && !o.comm && o.dense_split->grad_div <= 1.0;
   // the largest copy count of an item (in-batch: a positive drawn by every other row), the
   // split-f16 dz bounds' kD factor
   const double kd_max = b->layout == DCUE_LAYOUT_GATHER ? 1.0 + (double)B * N : 1.0;
@@ -1207,33 +1098,18 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // cost the chain a gap before its next kernel -- and each side stream's consumer follows a one-wave
   // relay (k_wait_signals) instead of a cross-queue event wait. fork_wait[l]: what the consumers of g_l
   // wait for (flag null: ev_layer[l]). Not with the A/B orders that hand ev_layer[3] on
-  // (DCUE_AHEAD_AT=fork, DCUE_FORK_ONCE, DCUE_SCORE_FORK) or SyncBN, which keep the events.
+  // (DCUE_AHEAD_AT=fork, DCUE_SCORE_FORK) or SyncBN, which keep the events.
   const bool fork_dev = o.sig && o.sig_issued && xq_edge_on(XQ_FORK) && !capturing_step() && !o.ahead &&
-                        !fork_once() && !o.sync_bn && !(o.score_done && *o.score_done) && !o.item_only;
+                        !o.sync_bn && !(o.score_done && *o.score_done) && !o.item_only;
   DevWait fork_wait[6] = {};
   // (DCUE_XQ_LATE) the late Adam's joins the same way: each weight-gradient stream's reduce is followed
   // by k_signal, and a relay ahead of the late Adam on the user stream waits for both words
   const bool late_dev = o.sig && o.sig_issued && xq_edge_on(XQ_LATE) && !capturing_step() && o.dense_split &&
-                        !o.comm && !late_join_hop();
+                        !o.comm;
   DevWait late_join[2] = {};  // wgrad streams 0 and 1
-  // DCUE_LATE_SIG_WG=1 (A/B): the reduces' workgroups signal themselves (WgradMulti::done_sig) instead
-  // of a k_signal launch behind each reduce -- 513 and about 1,000 agent-scope releases a step
-  static const bool late_sig_wg = [] {
-    const char* e = getenv("DCUE_LATE_SIG_WG");
-    return e && e[0] == '1';
-  }();
-  int late_blocks[2] = {1, 1};  // what each stream's launch adds to its word
   if (late_dev) {
-    if (late_sig_wg) {
-      late_blocks[1] = wgrad_reduce_blocks(H, H, layer_geom(2).ks);
-      late_blocks[0] = wgrad_reduce_blocks(D, H, layer_geom(5).ks);
-      for (int l = 3; l <= 4; ++l) late_blocks[0] += wgrad_reduce_blocks(H, H, layer_geom(l).ks);
-      if (!c.res && !c.text) late_blocks[0] += wgrad_reduce_blocks(D, D, 1);  // (the fc slot)
-    }
-    late_join[0] = DevWait{o.sig + kSigWgradHi, o.sig_issued[kSigWgradHi] += (unsigned)late_blocks[0],
-                           user_fwd_fail_flag()};
-    late_join[1] = DevWait{o.sig + kSigWgrad2, o.sig_issued[kSigWgrad2] += (unsigned)late_blocks[1],
-                           user_fwd_fail_flag()};
+    late_join[0] = DevWait{o.sig + kSigWgradHi, o.sig_issued[kSigWgradHi] += 1u, user_fwd_fail_flag()};
+    late_join[1] = DevWait{o.sig + kSigWgrad2, o.sig_issued[kSigWgrad2] += 1u, user_fwd_fail_flag()};
   }
   // user tower (userembedding.py:33-44 backward), the compact embedding rows, and -- when the step
   // carries it -- the user table's Adam step (it needs nothing from the item tower)
@@ -1284,7 +1160,6 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
     // deferred user-table Adam with the step (plans): the compact rows and their Adam step in one
     // launch (k_emb_grad_adam: each distinct user's workgroup sums its rows, then steps them)
     const bool emb_fused = o.emb_adam && m->emb_step && o.defer_flush_slice;
-    if (o.slice_done && *o.slice_done) TRY(wait_point(su, *o.slice_done));  // (a slice off this stream)
     {
       ForkAfter fk(sp, su, &tail[1]);
       if (emb_fused)
@@ -1382,13 +1257,8 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
       mw.db[j] = c.Gd(seg_conv_b(l));
     }
     if (late_dev) {  // the late Adam's relay waits for this stream's word (no event bound)
-      const int slot = lo == 2 ? kSigWgrad2 : kSigWgradHi;
-      if (late_sig_wg) {
-        mw.done_sig = o.sig + slot;
-        mw.done_blocks = late_blocks[lo == 2];
-      }
       TRY(launch_conv_wgrad_multi(mw, so));
-      if (!late_sig_wg) TRY(launch_signal(o.sig + slot, late_join[lo == 2].val, so));
+      TRY(launch_signal(o.sig + (lo == 2 ? kSigWgrad2 : kSigWgradHi), late_join[lo == 2].val, so));
     } else {
       ForkAfter fk(sp, so, tl);
       TRY(launch_conv_wgrad_multi(mw, so));
@@ -1406,9 +1276,7 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // for *late_done before conv 2). Other steps: the join -- wgrad stream 0 collects the user
   // stream's and wgrad stream 1's tails, and the caller's stream waits for it once (each
   // cross-queue wait on a pending event costs the waiting queue ≈4 µs, measured; on the side
-  // stream that time is slack, on the caller's it is the step's). DCUE_LATE_JOIN=hop keeps the join
-  // in split plans too, for the A/B.
-  const bool hop = late_join_hop();
+  // stream that time is slack, on the caller's it is the step's).
   // split plans without an exchange: the late Adam on the user stream waits for the prepared inputs
   // and the next launch waits for it before conv 1 (late_wait_at_conv1)
   const bool inputs_via_late = o.dense_split && !o.comm && o.late_done && late_wait_at_conv1();
@@ -1416,16 +1284,10 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // plans (split, no exchange): the late Adam also signals the next step's conv 2 (DevWait)
   DevWait late_sig{};
   // The late Adam's signal is a one-lane k_signal after the sweep: every workgroup of the sweep
-  // releasing its stores itself (dev_signal_wg, DCUE_LATE_SIG=kernel) costs an L2 writeback each on
-  // gfx950 -- 440 of them -- and measured 2-4 us slower per step (profiles/r06_ab_late_signal.txt)
-  static const bool late_sig_launch = [] {
-    const char* e = getenv("DCUE_LATE_SIG");
-    return !(e && e[0] == 'k');
-  }();
+  // releasing its stores itself costs an L2 writeback each on gfx950 -- 440 of them -- and measured
+  // 2-4 us slower per step (profiles/r06_ab_late_signal.txt)
   if (o.dense_split && !o.comm && o.late_sig && o.sig && !capturing_step()) {
-    // (DCUE_LATE_SIG=kernel: the sweep's workgroups signal themselves, k_adam_dense_pack)
-    const unsigned nwg = late_sig_launch ? 1u : (unsigned)adam_dense_blocks(c.poff[kSeg] - c.poff[DCUE_SEG_LATE]);
-    late_sig = DevWait{o.sig + kSigLate, o.sig_issued[kSigLate] += nwg, user_fwd_fail_flag()};
+    late_sig = DevWait{o.sig + kSigLate, o.sig_issued[kSigLate] += 1u, user_fwd_fail_flag()};
     *o.late_sig = late_sig;
   }
   dcue_adam_args dense = {};
@@ -1435,15 +1297,13 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   }
   const long late = c.poff[DCUE_SEG_LATE];
   auto late_part = [&]() -> int {
-    if (!o.dense_split || hop) {
+    if (!o.dense_split) {
       if (tail[1]) TRY(wait_point(sw[0], tail[1]));
       TRY(wait_point(sw[0], tail[3]));
       TRY(fork_point(sp, sw[0], &joined));
     }
     if (o.dense_split) {
-      if (hop) {
-        TRY(wait_point(su, joined));
-      } else if (late_dev) {
+      if (late_dev) {
         TRY(launch_wait_signals(late_join, 2, su));
       } else {
         TRY(wait_point(su, tail[2]));
@@ -1457,11 +1317,10 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
       TRY(debug_delay(DCUE_SITE_LATE_ADAM, su));
       {
         ForkAfter fk(sp, su, o.late_done);
-        TRY(launch_adam(m, &dense, c.poff, su, true, late, -1, !legacy_orders(),
-                        late_sig.flag && !late_sig_launch ? o.sig + kSigLate : nullptr));
+        TRY(launch_adam(m, &dense, c.poff, su, true, late, -1, !legacy_orders()));
         TRY(fk.done());
       }
-      if (late_sig.flag && late_sig_launch) TRY(launch_signal(o.sig + kSigLate, late_sig.val, su));
+      if (late_sig.flag) TRY(launch_signal(o.sig + kSigLate, late_sig.val, su));
       TRY(probe(PR_P_LATE, m->params + late, c.poff[kSeg] - late, su));
     }
     return DCUE_OK;
@@ -1573,7 +1432,7 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
       } else if (thr) {
         TRY(post(multi_2));
       }
-    } else if ((l - 1 == 3 && !fork_once()) || l - 1 == 2) {
+    } else if (l - 1 == 3 || l - 1 == 2) {
       TRY(debug_delay(l - 1 == 3 ? DCUE_SITE_DGRAD_4 : DCUE_SITE_DGRAD_3, s));
       ForkAfter fk(sp, s, &ev_layer[l - 1]);
       TRY(launch_conv_dgrad(l, l == 5 ? D : H, ra, s));
@@ -1583,21 +1442,14 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
         launch_tag().missed = true;
       }
       TRY(fk.done());
-      if (l - 1 == 3 && !fork_once()) {
+      if (l - 1 == 3) {
         if (thr) TRY(post(multi_hi));
         TRY(after_fork3());
-      }
-      if (l - 1 == 2) {
-        if (fork_once()) {
-          ev_layer[3] = ev_layer[2];
-          if (thr) TRY(post(multi_hi));
-          TRY(after_fork3());
-        }
-        if (thr) TRY(post(multi_2));
+      } else if (thr) {
+        TRY(post(multi_2));
       }
     } else {
       if (l == 2) TRY(debug_delay(DCUE_SITE_DGRAD_2, s));
-      if (l == 4) TRY(debug_delay(DCUE_SITE_DGRAD_4, s));  // (DCUE_FORK_ONCE: no fork point after it)
       TRY(launch_conv_dgrad(l, l == 5 ? D : H, ra, s));
       if (sync) TRY(comm_allreduce_u64(o.sync_bn, bn_acc(w.bnbacc, w.cmax, l - 1), 4L * w.cmax, s));
     }
@@ -1607,72 +1459,61 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   // plans: the next step's prepared inputs ordered by the conv-1 weight gradient's device-side wait
   // (k_conv_wgrad16t, DevWait) instead of a stream wait before it
   const bool inputs_dev = o.inputs_wait.flag != nullptr && f16w && !inputs_via_late && !capturing_step();
-  // conv weight gradient of layer l on stream `so` (its own split-K partial set `ps`); `tail`:
-  // a fork point after its last kernel
-  auto issue_wgrad = [&](int l, hipStream_t so, int ps, hipEvent_t* tail) -> int {
-    const LayerGeom gm = layer_geom(l);
-    const int C = l == 5 ? D : H;
-    const int cin = l == 1 ? kMels : H;
-    if (so != s) TRY(wait_point(so, ev_layer[l]));
+  // the step's tail on the caller's stream: the conv-1 weight gradient, its reduce, and bn0's
+  // gradients (+ the early segments' Adam); `tail`: a fork point after its last kernel
+  auto conv1_tail = [&](hipEvent_t* tail) -> int {
     HPROF("capi:18");
     WgradArgs wa = {};
     // split-f16 kernels: layer 1 reads the track table itself (bn0 applied at the fill), not xhat0
-    wa.xsrc = l == 1 ? (f16w ? t->data : (const void*)xhat0) : (const void*)w.y[l - 1];
+    wa.xsrc = f16w ? t->data : (const void*)xhat0;
     wa.item_track = b->item_track;
-    wa.x_mean = w.mean[l - 1];
-    wa.x_a = l == 1 ? w.invstd[0] : w.a[l - 1];
-    wa.x_beta = l == 1 ? nullptr : c.beta_bwd(w, l - 1);
-    wa.g_l = w.g[l]; wa.y_l = w.y[l]; wa.idx_l = w.idx[l];
-    wa.mean_l = w.mean[l]; wa.invstd_l = w.invstd[l]; wa.a_l = w.a[l];
-    wa.dz_acc = bn_acc(w.bnbacc, w.cmax, l); wa.dgamma = c.dgamma(w, l); wa.dbeta = c.dbeta(w, l);
-    wa.invN = c.bn ? (float)(1.0 / (copies * gm.lp)) : 0.f;
+    wa.x_mean = w.mean[0];
+    wa.x_a = w.invstd[0];
+    wa.g_l = w.g[1]; wa.y_l = w.y[1]; wa.idx_l = w.idx[1];
+    wa.mean_l = w.mean[1]; wa.invstd_l = w.invstd[1]; wa.a_l = w.a[1];
+    wa.dz_acc = bn_acc(w.bnbacc, w.cmax, 1); wa.dgamma = c.dgamma(w, 1); wa.dbeta = c.dbeta(w, 1);
+    wa.invN = c.bn ? (float)(1.0 / (copies * layer_geom(1).lp)) : 0.f;
     wa.bn_world = bn_world;
     wa.counts = w.counts;
-    wa.M = M; wa.cout = C; wa.cin = cin;
-    wa.wpart = w.wpart[ps]; wa.bpart = w.bpart[ps];
+    wa.M = M; wa.cout = H; wa.cin = kMels;
+    wa.wpart = w.wpart; wa.bpart = w.bpart;
     if (f16w) {
-      wa.x_range = rng_at(w, l - 1); wa.y_range = rng_at(w, l); wa.g_range = grng_at(w, l);
+      wa.x_range = rng_at(w, 0); wa.y_range = rng_at(w, 1); wa.g_range = grng_at(w, 1);
       wa.kd_max = kd_max * wa.invN;
     }
-    if (l == 1 && inputs_dev) wa.wait = o.inputs_wait;
-    const int nch = wgrad_nchunk(l, M, C, cin);
-    if (l == 1 && !f16w) {  // the GEMM reads the pooled BN1 backward, expanded to rows at MFMA time
-      TRY(launch_conv1_dx(wa, w.dx1, so));
+    if (inputs_dev) wa.wait = o.inputs_wait;
+    const int nch = wgrad_nchunk(1, M, H, kMels);
+    if (!f16w) {  // the GEMM reads the pooled BN1 backward, expanded to rows at MFMA time
+      TRY(launch_conv1_dx(wa, w.dx1, s));
       wa.g_l = w.dx1;
     }
     TimerScope tsc;
-    TRY(timer_begin(&tsc, l == 1 ? DCUE_TIMED_CONV1_WGRAD : -1, so));
+    TRY(timer_begin(&tsc, DCUE_TIMED_CONV1_WGRAD, s));
     HPROF("capi:19");
-    TRY(launch_conv_wgrad(l, l == 1 ? src : SRC_ACT, wa, nch, so));
+    TRY(launch_conv_wgrad(src, wa, nch, s));
     HPROF("capi:20");
     TRY(timer_end(&tsc));
     HPROF("capi:21");
-    if (l != 1) {
-      ForkAfter fk(sp, so, tail);
-      TRY(launch_wgrad_reduce(l, wa.wpart, wa.bpart, nch, C, cin, c.Gd(seg_conv_w(l)),
-                              c.Gd(seg_conv_b(l)), w.G, w.S, so));
-      return fk.done();
-    }
-    TRY(launch_wgrad_reduce(l, wa.wpart, wa.bpart, nch, C, cin, c.Gd(seg_conv_w(l)),
-                            c.Gd(seg_conv_b(l)), w.G, w.S, so));
-    ForkAfter fk(sp, so, tail);
+    TRY(launch_wgrad_reduce(1, wa.wpart, wa.bpart, nch, H, kMels, c.Gd(seg_conv_w(1)),
+                            c.Gd(seg_conv_b(1)), w.G, w.S, s));
+    ForkAfter fk(sp, s, tail);
     const bool graw = f16w && src == SRC_TRACK_F16;  // G over the raw fp16 input (conv_wgrad.hip)
     if (fuse_late) {  // split plans: bn0's gradients and Adam over [0, DCUE_SEG_LATE) in one launch
       Bn0Adam ba;
       ba.md = m; ba.poff = c.poff; ba.args = *o.dense_split; ba.bn = c.bn;
       TRY(launch_bn0_grads_adam(w.G, w.S, c.gamma(w, 0), c.beta(w, 0), graw ? w.mean[0] : nullptr,
-                                graw ? w.invstd[0] : nullptr, H, c.dgamma(w, 0), c.dbeta(w, 0), ba, so));
+                                graw ? w.invstd[0] : nullptr, H, c.dgamma(w, 0), c.dbeta(w, 0), ba, s));
       TRY(fk.done());
       if (!probes_on()) return DCUE_OK;
-      TRY(probe(PR_G_1, m->grads, late, so));
-      return probe(PR_P_EARLY, m->params, late, so);
+      TRY(probe(PR_G_1, m->grads, late, s));
+      return probe(PR_P_EARLY, m->params, late, s);
     }
     TRY(launch_bn0_grads(w.G, w.S, c.P(seg_conv_w(1)), c.gamma(w, 0), c.beta(w, 0),
                          graw ? w.mean[0] : nullptr, graw ? w.invstd[0] : nullptr, H,
                          c.Gd(seg_conv_w(1)), c.dgamma(w, 0), c.dbeta(w, 0),
-                         c.Gd(seg_conv_b(1)), so));
+                         c.Gd(seg_conv_b(1)), s));
     TRY(fk.done());
-    return probe(PR_G_1, m->grads, late, so);
+    return probe(PR_G_1, m->grads, late, s);
   };
   // layer 1 (the step's tail) follows the chain on the caller's stream, issued right away
   if (ev_x0) TRY(wait_point(s, ev_x0));
@@ -1684,12 +1525,11 @@ int backward_impl(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t
   }
   TRY(debug_delay(DCUE_SITE_WGRAD_1, s));
   // (split plans without an exchange: nothing waits for the caller stream's tail -- no event bound)
-  TRY(issue_wgrad(1, s, 2, o.dense_split && !o.comm ? nullptr : &tail[0]));
+  TRY(conv1_tail(o.dense_split && !o.comm ? nullptr : &tail[0]));
   HPROF("capi:22");
 
   if (!thr) {
     if (c.res || c.text) TRY(fc_text_wgrad());
-    if (fork_once()) ev_layer[3] = ev_layer[2];
     TRY(multi_hi());
     TRY(multi_2());
     HPROF("capi:25");

@@ -14,25 +14,21 @@ static constexpr int kWgradRch = 72;  // rows per chunk step (9 per thread)
 // the row dimension. Workgroup = 128 (o) x 128 (kc) output block x one chunk of rows; the chunk is
 // streamed through LDS RCH rows at a time (dz and x tiles, both built by fused elementwise loads);
 // each wave owns a 64x64 block (4x4 MFMA tiles). Partial blocks per chunk are summed by
-// k_wgrad_reduce in a fixed order (deterministic). EDGES (layer 1) also accumulates the per-output
-// sums of dz at the first/last two positions: with them the reduce recovers, per tap, the sum of dz
-// over positions whose input is not zero padding -- what bn0's beta gradient and the bn0 affine
-// split of dW1 need ("bn0 without conv1 dgrad").
-// The body takes its block coordinates (kc tile bx, o tile by, chunk bz) as arguments: k_conv_wgrad
-// runs one layer per launch, k_conv_wgrad_multi the weight gradients of layers 2-5 in one launch.
+// k_wgrad_reduce_multi in a fixed order (deterministic). x is the previous layer's output y_{l-1}
+// under BN_{l-1}'s affine (conv 1 has kernels of its own, k_conv1_wgrad and k_conv_wgrad16t).
+// The body takes its block coordinates (kc tile bx, o tile by, chunk bz) as arguments:
+// k_conv_wgrad_multi runs the weight gradients of layers 2-5 in one launch.
 // RAW: dz is g_l itself (no BatchNorm / ReLU / pool between): the fc layer's weight gradient,
 // dW[n][k] = sum over items of df[i][n] bn5(y5)[i][k], run as a 1x1 "conv" (k_conv_wgrad_multi slot
 // with layer 6) -- split-K over the items like the convs, where a row-serial small GEMM walked all
 // M rows in 16 workgroups.
-template <int SRCX, int KS, int PAD, int LIN, int R, int POOL, int LP, int RCH, bool EDGES, bool RAW = false>
+template <int KS, int PAD, int LIN, int R, int POOL, int LP, int RCH, bool RAW = false>
 __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, int bz, float* lds) {
   constexpr int PW = 128 + 16;  // == 16 (mod 32): ds_read_b32 rows r and r+1 on disjoint banks
-  constexpr int NB = EDGES ? 5 : 1;
   constexpr int FR = RCH / 8;   // rows per thread per chunk step (8 row slots x 32 channel quads)
-  constexpr bool TRACK = SRCX == SRC_TRACK_F16 || SRCX == SRC_TRACK_F32;
   float* dzs = lds;
   float* xs = lds + RCH * PW;
-  float (*bsum)[NB][128] = reinterpret_cast<float (*)[NB][128]>(lds + 2 * RCH * PW);  // [8][NB][128]
+  float (*bsum)[128] = reinterpret_cast<float (*)[128]>(lds + 2 * RCH * PW);  // [8][128]
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, l16 = lane & 15;
@@ -49,9 +45,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
   for (int m = 0; m < 4; ++m)
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float4 bacc[NB];
-#pragma unroll
-  for (int e = 0; e < NB; ++e) bacc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 bacc = make_float4(0.f, 0.f, 0.f, 0.f);
 
   // this thread fills channel quad q (dz outputs o..o+3, x columns kc..kc+3) of row slots
   // slot, slot+8, ...; everything per channel is loaded once, out of the row loop
@@ -89,7 +83,6 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
   auto issue = [&](long rb) {
     long ii[FR];
     int tt[FR], pc[FR];
-    int trk[FR];
 #pragma unroll
     for (int j = 0; j < FR; ++j) {
       long row = rb + slot + 8 * j;
@@ -98,10 +91,6 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
       tt[j] = (int)(row - ii[j] * R);
       const int p = tt[j] + kx - PAD;
       pc[j] = p < 0 ? 0 : (p >= LIN ? LIN - 1 : p);
-    }
-    if constexpr (TRACK) {
-#pragma unroll
-      for (int j = 0; j < FR; ++j) trk[j] = a.item_track[ii[j]];
     }
 #pragma unroll
     for (int j = 0; j < FR; ++j) {
@@ -112,15 +101,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
         rid[j] = *reinterpret_cast<const uint32_t*>(a.idx_l + base);
         rcnt[j] = a.counts ? a.counts[ii[j]] : 1.f;
       }
-      if constexpr (SRCX == SRC_TRACK_F16) {
-        const uint2 raw = *reinterpret_cast<const uint2*>(reinterpret_cast<const __half*>(a.xsrc) +
-                                                          (((long)trk[j] * kFrames + pc[j]) * kMels + cx));
-        rx[j] = make_float4(__uint_as_float(raw.x), __uint_as_float(raw.y), 0.f, 0.f);
-      } else if constexpr (SRCX == SRC_TRACK_F32) {
-        rx[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + (((long)trk[j] * kFrames + pc[j]) * kMels + cx));
-      } else {
-        rx[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + ((ii[j] * LIN + pc[j]) * cin + cx));
-      }
+      rx[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + ((ii[j] * LIN + pc[j]) * cin + cx));
     }
   };
 
@@ -139,7 +120,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
       if (valid && o_ok && RAW) {
         dz = rg[j];
         if (do_bias) {
-          bacc[0].x += dz.x; bacc[0].y += dz.y; bacc[0].z += dz.z; bacc[0].w += dz.w;
+          bacc.x += dz.x; bacc.y += dz.y; bacc.z += dz.z; bacc.w += dz.w;
         }
       } else if (valid && o_ok) {
         const float kD = rcnt[j] * a.invN;
@@ -157,29 +138,12 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
         }
         dz = make_float4(r4[0], r4[1], r4[2], r4[3]);
         if (do_bias) {
-          bacc[0].x += dz.x; bacc[0].y += dz.y; bacc[0].z += dz.z; bacc[0].w += dz.w;
-          if constexpr (EDGES) {  // static indices only: keeps bacc[] in registers
-            const int e = t == 0 ? 1 : t == 1 ? 2 : t == R - 2 ? 3 : t == R - 1 ? 4 : 0;
-#pragma unroll
-            for (int k = 1; k < NB; ++k) {
-              const float f = e == k ? 1.f : 0.f;
-              bacc[k].x += f * dz.x; bacc[k].y += f * dz.y; bacc[k].z += f * dz.z; bacc[k].w += f * dz.w;
-            }
-          }
+          bacc.x += dz.x; bacc.y += dz.y; bacc.z += dz.z; bacc.w += dz.w;
         }
       }
       if (valid && kc_ok && p >= 0 && p < LIN) {
-        float x[4];
-        if constexpr (SRCX == SRC_TRACK_F16) {
-          const uint32_t lo = __float_as_uint(rx[j].x), hi = __float_as_uint(rx[j].y);
-          const __half2 h0 = *reinterpret_cast<const __half2*>(&lo);
-          const __half2 h1 = *reinterpret_cast<const __half2*>(&hi);
-          x[0] = __low2float(h0); x[1] = __high2float(h0); x[2] = __low2float(h1); x[3] = __high2float(h1);
-        } else {
-          x[0] = rx[j].x; x[1] = rx[j].y; x[2] = rx[j].z; x[3] = rx[j].w;
-        }
-        xv = make_float4((x[0] - xmu.x) * xsc.x + xbe.x, (x[1] - xmu.y) * xsc.y + xbe.y,
-                         (x[2] - xmu.z) * xsc.z + xbe.z, (x[3] - xmu.w) * xsc.w + xbe.w);
+        xv = make_float4((rx[j].x - xmu.x) * xsc.x + xbe.x, (rx[j].y - xmu.y) * xsc.y + xbe.y,
+                         (rx[j].z - xmu.z) * xsc.z + xbe.z, (rx[j].w - xmu.w) * xsc.w + xbe.w);
       }
       const int rr = slot + 8 * j;
       st4(&dzs[rr * PW + 4 * q], dz);
@@ -216,29 +180,19 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& a, int bx, int by, i
       }
     }
   if (do_bias) {
-#pragma unroll
-    for (int e = 0; e < NB; ++e) st4(&bsum[slot][e][4 * q], bacc[e]);
+    st4(&bsum[slot][4 * q], bacc);
     __syncthreads();
     if (tid < 128 && obase + tid < cout) {
+      float v = 0.f;
 #pragma unroll
-      for (int e = 0; e < NB; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl) v += bsum[sl][e][tid];
-        a.bpart[((size_t)bz * NB + e) * cout + obase + tid] = v;
-      }
+      for (int sl = 0; sl < 8; ++sl) v += bsum[sl][tid];
+      a.bpart[(size_t)bz * cout + obase + tid] = v;
     }
   }
 }
 
-// LDS floats of the weight-gradient body: the dz and x tiles, then the bias partial sums
-constexpr size_t wgrad_lds_floats(int nb) { return (size_t)2 * kWgradRch * (128 + 16) + 8 * nb * 128; }
-
-template <int SRCX, int KS, int PAD, int LIN, int R, int POOL, int LP, int RCH, bool EDGES>
-__global__ __launch_bounds__(256) void k_conv_wgrad(WgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  wgrad_body<SRCX, KS, PAD, LIN, R, POOL, LP, RCH, EDGES>(a, blockIdx.x, blockIdx.y, blockIdx.z, lds);
-}
+// LDS bytes of the weight-gradient body: the dz and x tiles, then the bias partial sums
+constexpr size_t kWgradLdsB = ((size_t)2 * kWgradRch * (128 + 16) + 8 * 128) * sizeof(float);
 
 // Weight gradients of several conv layers (of 2..5) in one launch: a 1-D grid of the layers'
 // (kc tile, o tile, chunk) blocks in slot order; each layer keeps its own partial buffers, summed by
@@ -247,7 +201,7 @@ template <int L>  // L = 6: the fc layer (a 1x1 conv over bn5(y5) with dz = df, 
 __device__ __forceinline__ void wgrad_multi_layer(const WgradMulti& w, int j, int b, float* lds) {
   constexpr LayerGeom gm = layer_geom(L == 6 ? 5 : L);
   const int kt = w.kt[j], ot = w.ot[j];
-  wgrad_body<SRC_ACT, gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, gm.lp, kWgradRch, false, L == 6>(
+  wgrad_body<gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, gm.lp, kWgradRch, L == 6>(
       w.a[j], b % kt, (b / kt) % ot, b / (kt * ot), lds);
 }
 
@@ -323,24 +277,19 @@ __device__ __forceinline__ float w16_key(const unsigned* keys, int i) {
   return k ? ord_value(k) : 0.f;
 }
 
-template <int SRCX, int KS, int PAD, int LIN, int R, int POOL, int LP, bool EDGES, bool RAW = false>
+template <int KS, int PAD, int LIN, int R, int POOL, int LP, bool RAW = false>
 __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by, int bz, char* lds) {
   constexpr int RCH = kW16Rows;
-  constexpr int NB = EDGES ? 5 : 1;
   constexpr int FR = RCH / 8;          // x rows per thread per stage (8 row slots x 32 channel quads)
   constexpr int FW = RCH / POOL / 8;   // dz pool windows per thread per stage
   static_assert(RCH % (8 * POOL) == 0 && R % POOL == 0, "a stage holds whole pool windows");
-  constexpr bool TRACK = SRCX == SRC_TRACK_F16 || SRCX == SRC_TRACK_F32;
-  // an fp16 track table is its own exact fp16 operand: one image, no split, one MFMA fewer per
-  // product, and bn0's affine (x - mu0) * invstd0 is applied to the reduced sums (k_bn0_grads)
-  constexpr bool XRAW = SRCX == SRC_TRACK_F16;
   char* dzh = lds;
   char* dzl = lds + kW16ImgB;
   char* xh = lds + 2 * kW16ImgB;
   char* xl = lds + 3 * kW16ImgB;
   int* exp_o = reinterpret_cast<int*>(lds + 4 * kW16ImgB);
   int* exp_c = exp_o + 128;
-  float (*bsum)[NB][128] = reinterpret_cast<float (*)[NB][128]>(lds);  // after the last stage
+  float (*bsum)[128] = reinterpret_cast<float (*)[128]>(lds);  // after the last stage
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, l16 = lane & 15;
@@ -357,9 +306,7 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
   for (int m = 0; m < 4; ++m)
 #pragma unroll
     for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float4 bacc[NB];
-#pragma unroll
-  for (int e = 0; e < NB; ++e) bacc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 bacc = make_float4(0.f, 0.f, 0.f, 0.f);
 
   // this thread fills channel quad q (dz outputs o..o+3, x columns kc..kc+3): dz of pool windows
   // slot, slot+8, ... and x of row slots slot, slot+8, ...; everything per channel is set up once
@@ -407,16 +354,9 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
         bo = fabsf(av[s]) * (gmax + a.kd_max * (fabsf(sd[s]) + xhm * fabsf(sdx[s])));
       }
       eo[s] = o_ok ? w16_exp(bo) : 0;
-      float lo, hi;
-      if constexpr (TRACK) {
-        lo = -w16_key(a.x_range + kRngC, cx + s);
-        hi = w16_key(a.x_range, cx + s);
-      } else {
-        lo = 0.f;
-        hi = fmaxf(w16_key(a.x_range, cx + s), 0.f);
-      }
+      const float lo = 0.f, hi = fmaxf(w16_key(a.x_range, cx + s), 0.f);  // (a ReLU output)
       const float bx_ = fmaxf(fabsf((lo - xm[s]) * xs_[s] + xb[s]), fabsf((hi - xm[s]) * xs_[s] + xb[s]));
-      ec[s] = (kc_ok && !XRAW) ? w16_exp(bx_) : 0;
+      ec[s] = kc_ok ? w16_exp(bx_) : 0;
       const float so = ldexpf(1.f, eo[s]), sx = ldexpf(1.f, ec[s]);
       if constexpr (RAW) {
         cas[s] = so; cA[s] = 0.f; cB[s] = 0.f;
@@ -443,50 +383,9 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
   float4 wg[FW], wy[FW];
   uint32_t wid[FW];
   float wcnt[FW];
-  float4 xr[XRAW ? 1 : FR];
-  uint2 xr16[XRAW ? FR : 1];
+  float4 xr[FR];
   uint32_t xvalid = 0;
   auto issue = [&](int rb) {
-    if constexpr (R >= RCH && TRACK) {
-      // layer 1: a stage's rows span at most two items, ia = rb / R and ia + 1 -- one division, two
-      // item-id loads and two row bases per stage instead of one of each per row (32-bit offsets
-      // for the pooled operands; the table's needs 64 bits)
-      const int ia = rb / R, ra = (ia + 1) * R;  // ra: the first row of item ia + 1
-      const int ib = min(ia + 1, a.M - 1);
-      const float ca = (!RAW && a.counts) ? a.counts[ia] : 1.f, cb = (!RAW && a.counts) ? a.counts[ib] : 1.f;
-#pragma unroll
-      for (int j = 0; j < FW; ++j) {
-        int rw = rb + (slot + 8 * j) * POOL;
-        rw = rw < r_end ? rw : rb;
-        const bool nb = rw >= ra;
-        const int t0 = rw - (nb ? ra : ra - R);
-        const int base = ((nb ? ib : ia) * LP + t0 / POOL) * cout + oc;
-        wg[j] = ld4(a.g_l + base);
-        if constexpr (!RAW) {
-          wy[j] = ld4(a.y_l + base);
-          wid[j] = *reinterpret_cast<const uint32_t*>(a.idx_l + base);
-          wcnt[j] = nb ? cb : ca;
-        }
-      }
-      const long ta = a.item_track[ia], tb = a.item_track[ib];
-      uint32_t vm = 0;
-#pragma unroll
-      for (int j = 0; j < FR; ++j) {
-        const int row = rb + slot + 8 * j;
-        const int rowc = row < r_end ? row : rb;
-        const bool nb = rowc >= ra;
-        const int p = rowc - (nb ? ra : ra - R) + kx - PAD;
-        vm |= (row < r_end && kc_ok && p >= 0 && p < LIN) ? (1u << j) : 0u;
-        const int pc = p < 0 ? 0 : (p >= LIN ? LIN - 1 : p);
-        const long e = ((nb ? tb : ta) * kFrames + pc) * kMels + cx;
-        if constexpr (XRAW)
-          xr16[j] = *reinterpret_cast<const uint2*>(reinterpret_cast<const __half*>(a.xsrc) + e);
-        else
-          xr[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + e);
-      }
-      xvalid = vm;
-      return;
-    }
 #pragma unroll
     for (int j = 0; j < FW; ++j) {
       int rw = rb + (slot + 8 * j) * POOL;
@@ -512,23 +411,9 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
       pc[j] = p < 0 ? 0 : (p >= LIN ? LIN - 1 : p);
     }
     xvalid = vm;
-    if constexpr (TRACK) {
-      int trk[FR];
 #pragma unroll
-      for (int j = 0; j < FR; ++j) trk[j] = a.item_track[ii[j]];
-#pragma unroll
-      for (int j = 0; j < FR; ++j) {
-        const long e = ((long)trk[j] * kFrames + pc[j]) * kMels + cx;
-        if constexpr (XRAW)
-          xr16[j] = *reinterpret_cast<const uint2*>(reinterpret_cast<const __half*>(a.xsrc) + e);
-        else
-          xr[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + e);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < FR; ++j)
-        xr[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + (((long)ii[j] * LIN + pc[j]) * cin + cx));
-    }
+    for (int j = 0; j < FR; ++j)
+      xr[j] = ld4(reinterpret_cast<const float*>(a.xsrc) + (((long)ii[j] * LIN + pc[j]) * cin + cx));
   };
 
   // fragment read offsets: lane 4q'+p of its 16-lane group g supplies row (8g + 4h + q') of the
@@ -559,30 +444,7 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
         }
       }
       if (do_bias) {
-        bacc[0].x += d[0]; bacc[0].y += d[1]; bacc[0].z += d[2]; bacc[0].w += d[3];
-        if constexpr (EDGES) {  // t = 0, 1 (first window), R-2, R-1 (last): static indices only
-          int t0;
-          if constexpr (R >= RCH) {  // as in issue(): at most two items per stage
-            const int ra = (rb / R + 1) * R;
-            t0 = rw - (rw >= ra ? ra : ra - R);
-          } else {
-            t0 = rw - (rw / R) * R;
-          }
-          const bool first = t0 == 0, last = t0 == R - POOL;
-          float e1[4], e2[4], e3[4], e4[4];
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            const uint32_t r = (wid[j] >> (8 * s)) & 0xffu;
-            e1[s] = (first && r == 0u) ? d[s] : 0.f;
-            e2[s] = (first && r == 1u) ? d[s] : 0.f;
-            e3[s] = (last && r == (uint32_t)(POOL - 2)) ? d[s] : 0.f;
-            e4[s] = (last && r == (uint32_t)(POOL - 1)) ? d[s] : 0.f;
-          }
-          bacc[1].x += e1[0]; bacc[1].y += e1[1]; bacc[1].z += e1[2]; bacc[1].w += e1[3];
-          bacc[2 % NB].x += e2[0]; bacc[2 % NB].y += e2[1]; bacc[2 % NB].z += e2[2]; bacc[2 % NB].w += e2[3];
-          bacc[3 % NB].x += e3[0]; bacc[3 % NB].y += e3[1]; bacc[3 % NB].z += e3[2]; bacc[3 % NB].w += e3[3];
-          bacc[4 % NB].x += e4[0]; bacc[4 % NB].y += e4[1]; bacc[4 % NB].z += e4[2]; bacc[4 % NB].w += e4[3];
-        }
+        bacc.x += d[0]; bacc.y += d[1]; bacc.z += d[2]; bacc.w += d[3];
       }
       const w16_h4 h = {(_Float16)d[0], (_Float16)d[1], (_Float16)d[2], (_Float16)d[3]};
       const w16_h4 l = {(_Float16)(d[0] - (float)h[0]), (_Float16)(d[1] - (float)h[1]),
@@ -608,15 +470,11 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
     for (int j = 0; j < FR; ++j) {
       const bool ok = (xvalid >> j) & 1u;
       const int off = w16_off(slot + 8 * j, q >> 1) + qoff;
-      if constexpr (XRAW) {
-        *reinterpret_cast<uint2*>(xh + off) = ok ? xr16[j] : make_uint2(0u, 0u);
-      } else {
-        const float x[4] = {xr[j].x, xr[j].y, xr[j].z, xr[j].w};
-        float v[4];
+      const float x[4] = {xr[j].x, xr[j].y, xr[j].z, xr[j].w};
+      float v[4];
 #pragma unroll
-        for (int s = 0; s < 4; ++s) v[s] = ok ? (x[s] - xm[s]) * xas[s] + xbs[s] : 0.f;
-        w16_split_store(xh, xl, off, make_float4(v[0], v[1], v[2], v[3]));
-      }
+      for (int s = 0; s < 4; ++s) v[s] = ok ? (x[s] - xm[s]) * xas[s] + xbs[s] : 0.f;
+      w16_split_store(xh, xl, off, make_float4(v[0], v[1], v[2], v[3]));
     }
     __syncthreads();
     if (rb + RCH < r_end) issue(rb + RCH);  // next stage's loads fly while the MFMAs run
@@ -639,21 +497,13 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
         const int o0 = w16_off(r0, ch) + 8 * (fp & 1), o1 = w16_off(r0 + 4, ch) + 8 * (fp & 1);
         const w16_h4 h0 = w16_tr(xh, o0), h1 = w16_tr(xh, o1);
         const w16_h8 bh = w16_h8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-        if constexpr (XRAW) {
+        const w16_h4 l0 = w16_tr(xl, o0), l1 = w16_tr(xl, o1);
+        const w16_h8 bl = w16_h8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
 #pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[m], bh, acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bh, acc[m][n], 0, 0, 0);
-          }
-        } else {
-          const w16_h4 l0 = w16_tr(xl, o0), l1 = w16_tr(xl, o1);
-          const w16_h8 bl = w16_h8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[m], bh, acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bl, acc[m][n], 0, 0, 0);
-            acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bh, acc[m][n], 0, 0, 0);
-          }
+        for (int m = 0; m < 4; ++m) {
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[m], bh, acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bl, acc[m][n], 0, 0, 0);
+          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bh, acc[m][n], 0, 0, 0);
         }
       }
     }
@@ -677,48 +527,32 @@ __device__ __forceinline__ void wgrad16_body(const WgradArgs& a, int bx, int by,
       }
   }
   if (do_bias) {  // (the operand images are free: the last stage ended with a barrier)
-#pragma unroll
-    for (int e = 0; e < NB; ++e) st4(&bsum[slot][e][4 * q], bacc[e]);
+    st4(&bsum[slot][4 * q], bacc);
     __syncthreads();
     if (tid < 128 && obase + tid < cout) {
       const int eo = exp_o[tid];
+      float v = 0.f;
 #pragma unroll
-      for (int e = 0; e < NB; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl) v += bsum[sl][e][tid];
-        a.bpart[((size_t)bz * NB + e) * cout + obase + tid] = ldexpf(v, -eo);
-      }
+      for (int sl = 0; sl < 8; ++sl) v += bsum[sl][tid];
+      a.bpart[(size_t)bz * cout + obase + tid] = ldexpf(v, -eo);
     }
   }
-}
-
-template <int SRCX, int KS, int PAD, int LIN, int R, int POOL, int LP, bool EDGES>
-__global__ __launch_bounds__(256, 2) void k_conv_wgrad16(WgradArgs a) {
-  // the conv-1 weight gradient is the step's tail on the caller's stream: its waves take the issue
-  // slots the side-stream weight gradients (priority 0) share with it
-  critical_path_priority();
-  extern __shared__ __attribute__((aligned(16))) char lds16[];
-  // the kc tiles of one chunk read the same x rows and dz windows: consecutive logical blocks
-  // (kc tile fastest) on one XCD share its L2 instead of fetching them once per tile from HBM
-  const int gx = gridDim.x, gy = gridDim.y;
-  const int L = xcd_swizzle(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-  wgrad16_body<SRCX, KS, PAD, LIN, R, POOL, LP, EDGES>(a, L % gx, (L / gx) % gy, L / (gx * gy), lds16);
-  if constexpr (SRCX != SRC_ACT) dev_wait_order(a.wait);  // (as k_conv_wgrad16t, layer 1)
 }
 
 template <int L>
 __device__ __forceinline__ void wgrad16_multi_layer(const WgradMulti& w, int j, int b, char* lds) {
   constexpr LayerGeom gm = layer_geom(L == 6 ? 5 : L);
   const int kt = w.kt[j], ot = w.ot[j];
-  wgrad16_body<SRC_ACT, gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, gm.lp, false, L == 6>(
+  wgrad16_body<gm.ks, gm.pad, gm.lin, gm.lp * gm.pool, gm.pool, gm.lp, L == 6>(
       w.a[j], b % kt, (b / kt) % ot, b / (kt * ot), lds);
 }
 
-template <int OCC>
-__global__ __launch_bounds__(256, OCC) void k_conv_wgrad16_multi(WgradMulti w) {
+// two workgroups per CU (the layer-5 / fc branch spills 148 B per lane at that register budget)
+__global__ __launch_bounds__(256, 2) void k_conv_wgrad16_multi(WgradMulti w) {
   extern __shared__ __attribute__((aligned(16))) char lds16[];
-  const int b = xcd_swizzle(blockIdx.x, gridDim.x);  // a chunk's tiles on one XCD (k_conv_wgrad16)
+  // the kc tiles of one chunk read the same x rows and dz windows: consecutive logical blocks
+  // (kc tile fastest) on one XCD share its L2 instead of fetching them once per tile from HBM
+  const int b = xcd_swizzle(blockIdx.x, gridDim.x);
   int j = 0;
   while (j + 1 < w.n && b >= w.start[j + 1]) ++j;
   switch (w.layer[j]) {
@@ -1130,7 +964,8 @@ __device__ __forceinline__ void wgrad16t_body(const WgradArgs& a, int by, int bz
 
 template <int SRCX, int KS, int PAD, int LIN, int R, int POOL, int LP>
 __global__ __launch_bounds__(kW16tThreads, 1) void k_conv_wgrad16t(WgradArgs a) {
-  // layer 1 is the step's tail on the caller's stream (as k_conv_wgrad16); layer 2 a side stream's
+  // layer 1 is the step's tail on the caller's stream: its waves take the issue slots the side-stream
+  // weight gradients (priority 0) share with it; layer 2 a side stream's
   if constexpr (SRCX != SRC_ACT) critical_path_priority();
   extern __shared__ __attribute__((aligned(16))) char lds16t[];
   // a chunk's o tiles read the same x rows: consecutive logical blocks (o tile fastest) on one XCD
@@ -1139,310 +974,6 @@ __global__ __launch_bounds__(kW16tThreads, 1) void k_conv_wgrad16t(WgradArgs a) 
   wgrad16t_body<SRCX, KS, PAD, LIN, R, POOL, LP>(a, L % ot, L / ot, lds16t);
   // (plans, layer 1: the next step's prepared inputs -- only an order for the kernels after this one)
   if constexpr (SRCX != SRC_ACT) dev_wait_order(a.wait);
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Conv-1 weight gradient, one tap per workgroup (round 6). wgrad16t_body gives
-// a workgroup a 64 o x 512 kc tile, so the chip fills only through split-K: 33 chunks x 2 tiles at
-// the in-batch shape, 8.7 MB of partial blocks for a 0.26 MB dW, and a workgroup's 4 stages run at
-// one per CU. Here the dW is cut into 32 o x 128 c tiles (4 o tiles x 4 taps = 16 per chunk) of 256
-// threads, so ~16 chunks fill the chip: half the partial bytes, and the x and dz operands a chunk's
-// 16 tiles share are re-read from L2 (the tiles of a chunk are consecutive logical blocks: one XCD).
-// Operands, column scaling and the hi + lo split of dz are wgrad16t_body's (XRAW: x is the raw fp16
-// table, exact in f16); the partial layout is the same, so launch_wgrad_reduce and bn0's gradient
-// kernels read it unchanged. Two stages' loads are in flight (the stage work is a quarter of
-// wgrad16t's, so the L2 round trip is what a stage would otherwise wait on).
-constexpr int kW1kO = 32;         // o per workgroup
-constexpr int kW1kThreads = 256;  // 4 waves: o block (16) x c half (64)
-template <int R, int KS>
-constexpr size_t w1k_lds_bytes() {
-  // dz hi / lo images (64 rows x 128 B; the tile's 32 o use the first 64 B of a row), the x image
-  // (IMG rows x 256 B) and the o exponents; after the stages the same bytes hold the tile (32 rows
-  // of 128 + 4 floats), then the bias partials (16 x 5 x 32 floats)
-  const size_t st = (size_t)2 * kW16Rows * 128 + (size_t)w16t_img_rows<R, KS>() * 256 + kW1kO * sizeof(int) +
-                    (size_t)kWgItems * (sizeof(int) + sizeof(float));
-  const size_t ep = (size_t)kW1kO * (128 + 4) * sizeof(float);
-  const size_t bs = (size_t)16 * 5 * kW1kO * sizeof(float);
-  const size_t m = st > ep ? st : ep;
-  return m > bs ? m : bs;
-}
-
-template <int KS, int PAD, int LIN, int R, int POOL, int LP>
-__device__ __forceinline__ void wgrad1k_body(const WgradArgs& a, int ot, int kx, int bz, char* lds) {
-  constexpr int RCH = kW16Rows;
-  constexpr int NB = 5;  // bias + the four edge sums (conv 1's zero padding)
-  constexpr int HALO = KS - 1;
-  constexpr int IMG = w16t_img_rows<R, KS>();
-  constexpr int FX = (IMG + 7) / 8;  // x image rows per thread (8 row slots x 32 channel quads)
-  static_assert(KS == 4 && POOL == 4 && R % POOL == 0 && R >= RCH, "conv 1: 16 windows a stage, at most two items");
-  char* dzh = lds;
-  char* dzl = dzh + RCH * 128;
-  char* xh = dzl + RCH * 128;
-  int* exp_o = reinterpret_cast<int*>(xh + IMG * 256);
-  int* trk_s = exp_o + kW1kO;  // the chunk's items' track ids and counts (the host bounds their number)
-  float* cnt_s = reinterpret_cast<float*>(trk_s + kWgItems);
-  float (*bsum)[NB][kW1kO] = reinterpret_cast<float (*)[NB][kW1kO]>(lds);  // after the tile's stores
-
-  DCUE_KTW(0, 6);
-  DCUE_KT(0, 0);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = lane >> 4, l16 = lane & 15;
-  const int ob = wave & 1, chh = wave >> 1;  // this wave's o block (16 o) and c half (64 c)
-  const int cout = a.cout;
-  const int obase = ot * kW1kO;
-  const int total = a.M * R;  // rows (the host keeps M * R below 2^30)
-  const int r_begin = bz * a.rows_per_chunk;  // a multiple of RCH
-  const int r_end = min(r_begin + a.rows_per_chunk, total);
-  const int item0 = r_begin / R;
-
-  f32x4 acc[4];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float4 bacc[NB];
-#pragma unroll
-  for (int e = 0; e < NB; ++e) bacc[e] = make_float4(0.f, 0.f, 0.f, 0.f);
-
-  // dz: threads 0..127, window slot ws (16 a stage) x o quad q (8); x: every thread, row slot xs (8)
-  // x channel quad cq (32)
-  const bool dzt = tid < 128;
-  const int q = tid & 7, ws = (tid >> 3) & 15;
-  const int o = obase + 4 * q;
-  const bool o_ok = o < cout;
-  const int oc = o_ok ? o : 0;
-  const int cq = tid & 31, xs = tid >> 5;
-  const int cx = 4 * cq;
-  struct StageRegs {
-    float4 wg, wy;
-    uint32_t wid;
-    float wcnt;
-    uint2 xr[FX];
-    uint32_t xvalid;
-  };
-  StageRegs s0 = {}, s1 = {};
-  // One stage's raw operands. Every thread issues the same loads on every path (threads 128..255 load
-  // a copy of threads 0..127's windows; a stage past the chunk reloads its first): the compiler's
-  // wait counts merge paths conservatively, so a load skipped on one path made every stage wait for
-  // all loads in flight -- the other stage's too -- which undid the two-stage pipeline
-  auto issue = [&](StageRegs& S, int rb_) {
-    const int rb = rb_ < r_end ? rb_ : r_begin;
-    const int i0 = rb / R, D = rb - i0 * R;  // the stage starts D rows into item i0
-    {
-      int rw = rb + ws * POOL;
-      rw = rw < r_end ? rw : rb;
-      const int ii = rw / R, t0 = rw - ii * R;
-      const int base = (ii * LP + t0 / POOL) * cout + oc;
-      S.wg = ld4(a.g_l + base);
-      S.wy = ld4(a.y_l + base);
-      S.wid = *reinterpret_cast<const uint32_t*>(a.idx_l + base);
-      S.wcnt = cnt_s[ii - item0];
-    }
-    // (track ids from LDS: a dependent global load here would make the stage's x loads wait for it,
-    // and loads retire in order, so for every load in flight before it -- the other stage's)
-    const long t_a = trk_s[i0 - item0], t_b = trk_s[min(i0 + 1, a.M - 1) - item0];
-    uint32_t vm = 0;
-#pragma unroll
-    for (int j = 0; j < FX; ++j) {
-      const int jr = xs + 8 * j;                       // image row
-      const int k = jr + D >= R + HALO ? 1 : 0;        // items after i0
-      const int i = i0 + k;
-      const int p = jr + D - k * (R + HALO) - PAD;     // input position in item i
-      const bool ok = jr < IMG && i < a.M && p >= 0 && p < LIN;
-      vm |= ok ? (1u << j) : 0u;
-      const long e = ((k ? t_b : t_a) * kFrames + (ok ? p : 0)) * kMels + cx;
-      S.xr[j] = *reinterpret_cast<const uint2*>(reinterpret_cast<const __half*>(a.xsrc) + e);
-    }
-    S.xvalid = vm;
-  };
-
-  // the column constants' loads first, then the first two stages' (loads return in issue order)
-  float mu[4], iv[4], av[4], sd[4], sdx[4], gmx[4], ymx[4];
-  {
-    const float4 m4 = ld4(a.mean_l + oc), i4 = ld4(a.invstd_l + oc), a4 = ld4(a.a_l + oc);
-    mu[0] = m4.x; mu[1] = m4.y; mu[2] = m4.z; mu[3] = m4.w;
-    iv[0] = i4.x; iv[1] = i4.y; iv[2] = i4.z; iv[3] = i4.w;
-    av[0] = a4.x; av[1] = a4.y; av[2] = a4.z; av[3] = a4.w;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      sd[s] = (float)acc_sum(a.dz_acc, cout, 0, oc + s);
-      sdx[s] = (float)acc_sum(a.dz_acc, cout, 1, oc + s);
-      gmx[s] = w16_key(a.g_range, oc + s);
-      ymx[s] = w16_key(a.y_range, oc + s);
-    }
-  }
-  {
-    const int nitem = min(a.M - item0, (r_end - 1) / R - item0 + 2);
-    for (int k = tid; k < nitem; k += kW1kThreads) {
-      trk_s[k] = a.item_track[item0 + k];
-      cnt_s[k] = a.counts ? a.counts[item0 + k] : 1.f;
-    }
-  }
-  __syncthreads();
-  issue(s0, r_begin);
-  issue(s1, r_begin + RCH);
-  if (ot == 0 && kx == 0 && bz == 0 && tid < cout) {  // BN_1 = gamma * xhat + beta: dbeta = sum g, dgamma = sum g * xhat
-    a.dbeta[tid] = (float)(acc_sum(a.dz_acc, cout, 0, tid) * bn_grad_scale(a));
-    a.dgamma[tid] = (float)(acc_sum(a.dz_acc, cout, 1, tid) * bn_grad_scale(a));
-  }
-  // scaled dz = cas g - count (cA + xhat cB), as wgrad16t_body (x: raw fp16, exponent 0)
-  float cas[4], cA[4], cB[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    const float ym = fmaxf(ymx[s], 0.f);
-    const float xhm = fmaxf(fabsf(mu[s]), fabsf(ym - mu[s])) * iv[s];
-    const float bo = fabsf(av[s]) * (gmx[s] + a.kd_max * (fabsf(sd[s]) + xhm * fabsf(sdx[s])));
-    const int eo = o_ok ? w16_exp(bo) : 0;
-    const float so = ldexpf(1.f, eo);
-    cas[s] = av[s] * so;
-    cA[s] = av[s] * a.invN * sd[s] * so;
-    cB[s] = av[s] * a.invN * sdx[s] * so;
-    if (tid < 8) exp_o[4 * q + s] = eo;
-  }
-  __syncthreads();
-  DCUE_KT(0, 1);
-
-  // fragment read offsets: lane 4q'+p of its 16-lane group g supplies row (8g + 4h + q') of the
-  // k-step, columns 4p..4p+3 of the 16-column tile
-  const int fq = l16 >> 2, fp = l16 & 3;
-  auto stage = [&](StageRegs& S, int rb) {
-    if (dzt) {  // dz: BN_1's backward for the thread's window, scaled, split, written to its rows
-      const int rw = rb + ws * POOL;
-      const bool wv = rw < r_end && o_ok;
-      const float gv[4] = {S.wg.x, S.wg.y, S.wg.z, S.wg.w}, yv[4] = {S.wy.x, S.wy.y, S.wy.z, S.wy.w};
-      float d[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const float xh_ = (yv[s] - mu[s]) * iv[s];
-        const float v = cas[s] * gv[s] - S.wcnt * (cA[s] + xh_ * cB[s]);
-        d[s] = (wv && yv[s] > 0.f) ? v : 0.f;
-      }
-      bacc[0].x += d[0]; bacc[0].y += d[1]; bacc[0].z += d[2]; bacc[0].w += d[3];
-      {  // t = 0, 1 (first window), R-2, R-1 (last window)
-        const int t0 = rw - (rw / R) * R;
-        const bool first = t0 == 0, last = t0 == R - POOL;
-        float e1[4], e2[4], e3[4], e4[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const uint32_t r = (S.wid >> (8 * s)) & 0xffu;
-          e1[s] = (first && r == 0u) ? d[s] : 0.f;
-          e2[s] = (first && r == 1u) ? d[s] : 0.f;
-          e3[s] = (last && r == (uint32_t)(POOL - 2)) ? d[s] : 0.f;
-          e4[s] = (last && r == (uint32_t)(POOL - 1)) ? d[s] : 0.f;
-        }
-        bacc[1].x += e1[0]; bacc[1].y += e1[1]; bacc[1].z += e1[2]; bacc[1].w += e1[3];
-        bacc[2].x += e2[0]; bacc[2].y += e2[1]; bacc[2].z += e2[2]; bacc[2].w += e2[3];
-        bacc[3].x += e3[0]; bacc[3].y += e3[1]; bacc[3].z += e3[2]; bacc[3].w += e3[3];
-        bacc[4].x += e4[0]; bacc[4].y += e4[1]; bacc[4].z += e4[2]; bacc[4].w += e4[3];
-      }
-      const w16_h4 h = {(_Float16)d[0], (_Float16)d[1], (_Float16)d[2], (_Float16)d[3]};
-      const w16_h4 l = {(_Float16)(d[0] - (float)h[0]), (_Float16)(d[1] - (float)h[1]),
-                        (_Float16)(d[2] - (float)h[2]), (_Float16)(d[3] - (float)h[3])};
-      const uint2 hb = __builtin_bit_cast(uint2, h), lb = __builtin_bit_cast(uint2, l);
-#pragma unroll
-      for (int jp = 0; jp < POOL; ++jp) {  // the window's argmax row carries it, the others zeros
-        const uint32_t m0 = ((S.wid & 0xffu) == (uint32_t)jp ? 0x0000ffffu : 0u) |
-                            (((S.wid >> 8) & 0xffu) == (uint32_t)jp ? 0xffff0000u : 0u);
-        const uint32_t m1 = (((S.wid >> 16) & 0xffu) == (uint32_t)jp ? 0x0000ffffu : 0u) |
-                            ((S.wid >> 24) == (uint32_t)jp ? 0xffff0000u : 0u);
-        const int off = w16_off128(ws * POOL + jp, q >> 1) + 8 * (q & 1);
-        *reinterpret_cast<uint2*>(dzh + off) = make_uint2(hb.x & m0, hb.y & m1);
-        *reinterpret_cast<uint2*>(dzl + off) = make_uint2(lb.x & m0, lb.y & m1);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < FX; ++j) {  // x image (zero padding and past-the-batch rows are zeros)
-      const int jr = xs + 8 * j;
-      if (jr < IMG) {
-        const bool ok = (S.xvalid >> j) & 1u;
-        *reinterpret_cast<uint2*>(xh + w16_off(jr, cq >> 1) + 8 * (cq & 1)) = ok ? S.xr[j] : make_uint2(0u, 0u);
-      }
-    }
-    __syncthreads();
-    if (rb == r_begin) DCUE_KT(0, 2);
-    const int lb = (rb / R + 1) * R - rb;  // the stage row where the next item starts
-    issue(S, rb + 2 * RCH);  // (S is in LDS: its registers take stage + 2)
-#pragma unroll
-    for (int ks = 0; ks < RCH / 32; ++ks) {
-      const int r0 = 32 * ks + 8 * g + fq;  // this lane's conv rows: r0 (first read), r0 + 4 (second)
-      const int ch = 2 * ob + (fp >> 1);
-      const int o0 = w16_off128(r0, ch) + 8 * (fp & 1), o1 = w16_off128(r0 + 4, ch) + 8 * (fp & 1);
-      const w16_h4 h0 = w16_tr(dzh, o0), h1 = w16_tr(dzh, o1), l0 = w16_tr(dzl, o0), l1 = w16_tr(dzl, o1);
-      const w16_h8 ah = w16_h8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
-      const w16_h8 al = w16_h8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
-      const int img0 = r0 + kx + (r0 >= lb ? HALO : 0), img1 = r0 + 4 + kx + (r0 + 4 >= lb ? HALO : 0);
-#pragma unroll
-      for (int n = 0; n < 4; ++n) {
-        const int cc = 2 * (4 * chh + n) + (fp >> 1);
-        const int ob0 = w16_off(img0, cc) + 8 * (fp & 1), ob1 = w16_off(img1, cc) + 8 * (fp & 1);
-        const w16_h4 x0 = w16_tr(xh, ob0), x1 = w16_tr(xh, ob1);
-        const w16_h8 bh = w16_h8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc[n], 0, 0, 0);
-        acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc[n], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  };
-  // stages in pairs: a chunk's odd last stage is paired with an empty one (every dz masked: it adds
-  // zeros), so the two register sets alternate on every path
-  for (int rb = r_begin; rb < r_end; rb += 2 * RCH) {
-    stage(s0, rb);
-    stage(s1, rb + RCH);
-  }
-
-  DCUE_KT(0, 3);
-  // partial block -> wpart[z][o][kx * 128 + c], unscaled; D lane map: o = 4g + reg, c = l16. The
-  // tile's 32 rows of 128 floats go through LDS (row pitch 132: the four g rows of a store land on
-  // disjoint banks) and out as linear float4 stores (512-byte row segments)
-  int eo_r[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) eo_r[j] = exp_o[16 * ob + 4 * g + j];
-  const int eo_bias = tid < kW1kO ? exp_o[tid] : 0;
-  __syncthreads();  // (the exponents are read: the tile overwrites them)
-  {
-    constexpr int PITCH = 128 + 4, KC = KS * 128;
-    float* tl = reinterpret_cast<float*>(lds);
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        tl[(16 * ob + 4 * g + j) * PITCH + 16 * (4 * chh + n) + l16] = ldexpf(acc[n][j], -eo_r[j]);
-    __syncthreads();
-    const int nrow = min(kW1kO, cout - obase);
-    float* wp = a.wpart + ((size_t)bz * cout + obase) * KC + kx * 128;
-    for (int i = tid; i < nrow * 32; i += kW1kThreads) {
-      const int r = i >> 5, k4 = i & 31;
-      st4(wp + (size_t)r * KC + 4 * k4, *reinterpret_cast<const float4*>(tl + r * PITCH + 4 * k4));
-    }
-  }
-  if (kx == 0) {  // bias (+ edge) partials: the tap-0 workgroups (every tap sees the same dz)
-    __syncthreads();  // (bsum reuses the tile's LDS)
-    if (dzt)
-#pragma unroll
-      for (int e = 0; e < NB; ++e) st4(&bsum[ws][e][4 * q], bacc[e]);
-    __syncthreads();
-    if (tid < kW1kO && obase + tid < cout) {
-#pragma unroll
-      for (int e = 0; e < NB; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int sl = 0; sl < 16; ++sl) v += bsum[sl][e][tid];  // the 16 window slots, in order
-        a.bpart[((size_t)bz * NB + e) * cout + obase + tid] = ldexpf(v, -eo_bias);
-      }
-    }
-  }
-  DCUE_KT(0, 4);
-  DCUE_KTW(0, 7);
-}
-
-template <int KS, int PAD, int LIN, int R, int POOL, int LP>
-__global__ __launch_bounds__(kW1kThreads, 2) void k_conv_wgrad1k(WgradArgs a) {
-  critical_path_priority();  // the step's tail on the caller's stream
-  extern __shared__ __attribute__((aligned(16))) char lds1k[];
-  // a chunk's 16 tiles (o tile fastest, then tap) are consecutive logical blocks: one XCD, one L2
-  const int ot = (a.cout + kW1kO - 1) / kW1kO;
-  const int L = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int tile = L % (ot * KS);
-  wgrad1k_body<KS, PAD, LIN, R, POOL, LP>(a, tile % ot, tile / ot, L / (ot * KS), lds1k);
-  dev_wait_order(a.wait);  // (plans: the next step's prepared inputs -- an order for later kernels only)
 }
 
 // whether the weight gradients run on split-f16 MFMA (DCUE_WGRAD_F16=0: the f32-MFMA kernels)
@@ -1455,15 +986,9 @@ bool wgrad_f16_on() {
 }
 
 // the layers whose split-f16 weight gradient runs tap-fused (k_conv_wgrad16t): 1 and 2, whose
-// inputs have 128 channels (layer 2 at H = 128). DCUE_W16_TAPFUSED=0: neither, =1: layer 1 only
-// (A/B; the kc-tiled k_conv_wgrad16 / multi kernel otherwise)
+// inputs have 128 channels (layer 2 at H = 128); the kc-tiled multi kernel otherwise
 static bool w16t_layer(int layer, int cin) {
-  static const int mode = [] {
-    const char* e = getenv("DCUE_W16_TAPFUSED");
-    return e ? atoi(e) : 2;
-  }();
-  if (!wgrad_f16_on() || cin != kMels) return false;
-  return layer == 1 ? mode >= 1 : (layer == 2 && mode >= 2);
+  return wgrad_f16_on() && cin == kMels && (layer == 1 || layer == 2);
 }
 
 // split-K chunk length of the split-f16 kernels: whole stages (so whole pool windows), (wgrad_nchunk
@@ -1478,7 +1003,6 @@ static long w16_rows_per_chunk(long rows, int nchunk) {
 static long wgrad_chunk_rows(int kernel, long rows, int nchunk) {
   switch (kernel) {
     case WK_CONV1: return 4L * ((rows / 4 + nchunk - 1) / nchunk);  // whole pool windows
-    case WK_F32:
     case WK_MULTI_F32: return (rows + nchunk - 1) / nchunk;  // the last chunk may be short; rows past it are masked
     default: return w16_rows_per_chunk(rows, nchunk);
   }
@@ -1826,18 +1350,6 @@ int launch_xhat0(int src, const void* tracks, const int32_t* item_track, int M, 
   return DCUE_OK;
 }
 
-// conv 1's split-f16 weight gradient on k_conv_wgrad1k (one tap per workgroup, round 6; needs
-// 128 input channels and cout <= 256) under DCUE_W1K=1. Off by default: at the in-batch shape it
-// measured 24.6-34.5 us (2-16 stages a chunk) against k_conv_wgrad16t's 19.9 us, although it writes
-// half the partial bytes (profiles/r06_w1k_sweep.txt).
-static bool w1k_layer1(int cin, int cout) {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_W1K");
-    return e && e[0] == '1';
-  }();
-  return on && wgrad_f16_on() && cin == kMels && cout % 4 == 0 && cout <= kW1kThreads;
-}
-
 // bound: the count before the whole-stage rounding below -- never under the launch's count and, unlike
 // it, never smaller for a larger M (993 items at H = 32 round 512 chunks of conv 1 down to 410, 992
 // keep 512): what a workspace for "up to M items" is sized by
@@ -1847,71 +1359,25 @@ int wgrad_nchunk(int layer, int M, int cout, int cin, bool bound) {
   const LayerGeom gm = layer_geom(layer == 6 ? 5 : layer);
   const long rows = (long)M * gm.lp * gm.pool;
   if (layer == 1 && !wgrad_f16_on()) {  // k_conv1_wgrad: 64x64 tiles, >= 4 steps per chunk, <= ~512 workgroups (2 per CU)
-    // tuning diagnostic: DCUE_W1_CHUNKS=n caps the split-K chunk count (A/B runs; the workspace is
-    // sized through this same function, so it follows)
-    static const long forced = [] {
-      const char* e = getenv("DCUE_W1_CHUNKS");
-      const long v = e ? atol(e) : 0;
-      return v >= 1 && v <= 64 ? v : 0L;
-    }();
     const long tiles1 = (4L * kMels / kW1Tile) * ((cout + kW1Tile - 1) / kW1Tile);
-    long n = forced ? forced : 512 / tiles1;
+    long n = 512 / tiles1;
     const long wins = (long)M * gm.lp;
     if (n > (wins + 4 * kW1Win - 1) / (4 * kW1Win)) n = (wins + 4 * kW1Win - 1) / (4 * kW1Win);
-    return (int)(n < 1 ? 1 : n);
-  }
-  if (layer == 1 && w1k_layer1(cin, cout)) {
-    // k_conv_wgrad1k: 16 tiles a chunk (4 o tiles x 4 taps at H = 128), two workgroups per CU, and
-    // at least DCUE_W1K_MIN_STAGES (default 8) 64-row stages a chunk: each chunk writes a 0.26 MB
-    // partial block, so the split-K depth is held down (in-batch: 15 chunks, 3.9 MB of partials
-    // against rounds 3-5's 33 and 8.7 MB)
-    static const long min_st = [] {
-      const char* e = getenv("DCUE_W1K_MIN_STAGES");
-      const long v = e ? atol(e) : 0;
-      return v >= 1 && v <= 256 ? v : 8L;
-    }();
-    const long tiles1 = ((cout + kW1kO - 1) / kW1kO) * gm.ks;
-    long n = 512 / tiles1;
-    const long per = min_st * kW16Rows;
-    if (n > (rows + per - 1) / per) n = (rows + per - 1) / per;
-    const long cap = (8L << 20) / ((long)cout * gm.ks * cin);
-    if (n > cap) n = cap;
-    // a chunk's items fit the kernel's LDS table: rows_per_chunk <= (kWgItems - 3) R
-    const long rmax = ((long)(kWgItems - 3) * gm.lp * gm.pool) / kW16Rows * kW16Rows;
-    if (n < (rows + rmax - 1) / rmax) n = (rows + rmax - 1) / rmax;
-    if (n < 1) n = 1;
-    if (!bound) n = (rows + w16_rows_per_chunk(rows, (int)n) - 1) / w16_rows_per_chunk(rows, (int)n);
     return (int)(n < 1 ? 1 : n);
   }
   const long tiles = w16t_layer(layer, cin)
                         ? (cout + kW16tO - 1) / kW16tO  // k_conv_wgrad16t: 64 o x all taps
                         : ((gm.ks * cin + 127) / 128) * ((cout + 127) / 128);
   // split-f16 kernels: two workgroups per CU (one's MFMAs and fill run while the other's stage
-  // loads are in flight); DCUE_W16_WGS_PER_CU=1 halves the chunks (A/B diagnostic)
-  static const long per_cu = [] {
-    const char* e = getenv("DCUE_W16_WGS_PER_CU");
-    return e && atoi(e) == 1 ? 1L : 2L;
-  }();
-  long n = (wgrad_f16_on() ? 256 * per_cu : 256) / tiles;
+  // loads are in flight)
+  long n = (wgrad_f16_on() ? 512 : 256) / tiles;
   if (!wgrad_f16_on()) {
     if (n > (rows + 63) / 64) n = (rows + 63) / 64;
   } else {
-    // at least DCUE_W16_MIN_STAGES (default 4) 64-row stages per chunk: each chunk costs a
-    // prologue, a partial block written and read back by the reduce, so short ones do not pay
-    // (A/B, GPU-only: 1, 2, 4 stages within noise in-batch; 4 the fastest catalogue, -8 us)
-    static const long min_stages = [] {
-      const char* e = getenv("DCUE_W16_MIN_STAGES");
-      const long v = e ? atol(e) : 0;
-      return v >= 1 && v <= 64 ? v : 4L;
-    }();
-    // DCUE_W16T_MIN_STAGES: the same for the tap-fused conv-1 kernel (A/B diagnostic)
-    static const long min_stages_t = [] {
-      const char* e = getenv("DCUE_W16T_MIN_STAGES");
-      const long v = e ? atol(e) : 0;
-      return v >= 1 && v <= 64 ? v : 0L;
-    }();
-    const bool fused = w16t_layer(layer, cin);
-    const long per = (fused && min_stages_t ? min_stages_t : min_stages) * kW16Rows;
+    // at least four 64-row stages per chunk: each chunk costs a prologue, a partial block written
+    // and read back by the reduce, so short ones do not pay (A/B, GPU-only: 1, 2, 4 stages within
+    // noise in-batch; 4 the fastest catalogue, -8 us)
+    const long per = 4 * kW16Rows;
     if (n > (rows + per - 1) / per) n = (rows + per - 1) / per;
   }
   const long cap = (8L << 20) / ((long)cout * gm.ks * cin);
@@ -1927,51 +1393,25 @@ int wgrad_nchunk(int layer, int M, int cout, int cin, bool bound) {
 }
 
 // The kernel (WK_*) of layer `layer`'s weight gradient in a training step: layer 1 in a launch of its
-// own (launch_conv_wgrad, `src` its track table's type); layer 2 alone and layers 3..6 together in
-// launch_conv_wgrad_multi (`alone`: the only layer of its launch)
-int wgrad_kernel(int layer, int cin, int cout, int src, bool alone) {
-  if (layer == 1) {
-    if (!wgrad_f16_on()) return WK_CONV1;
-    if (src == SRC_TRACK_F16 && w1k_layer1(cin, cout)) return WK_1K;
-    return w16t_layer(1, cin) ? WK_16T : WK_16;
-  }
+// own (launch_conv_wgrad); layer 2 alone and layers 3..6 together in launch_conv_wgrad_multi
+// (`alone`: the only layer of its launch)
+int wgrad_kernel(int layer, int cin, bool alone) {
+  if (layer == 1) return wgrad_f16_on() ? WK_16T : WK_CONV1;
   if (alone && layer == 2 && w16t_layer(2, cin)) return WK_16T;  // layer 2 alone: tap-fused + its reduce
   return wgrad_f16_on() ? WK_MULTI_F16 : WK_MULTI_F32;
 }
 
 // dcue_debug_launch_shape: the kernel, chunk count, chunk length and last chunk's rows of that launch
-void wgrad_shape(int layer, int M, int cout, int cin, int src, bool alone, int32_t* out) {
+void wgrad_shape(int layer, int M, int cout, int cin, bool alone, int32_t* out) {
   const LayerGeom gm = layer_geom(layer == 6 ? 5 : layer);
   const long rows = (long)M * gm.lp * gm.pool;
-  const int kernel = wgrad_kernel(layer, cin, cout, src, alone);
+  const int kernel = wgrad_kernel(layer, cin, alone);
   const int nchunk = wgrad_nchunk(layer, M, cout, cin);
   const long rpc = wgrad_chunk_rows(kernel, rows, nchunk);
   out[0] = kernel;
   out[1] = nchunk;
   out[2] = (int32_t)rpc;
   out[3] = (int32_t)(rows - (nchunk - 1) * rpc);
-}
-
-template <int L, int SRCX>
-static int wgrad_layer(const WgradArgs& a0, int nchunk, hipStream_t s) {
-  constexpr LayerGeom gm = layer_geom(L);
-  constexpr int R = gm.lp * gm.pool;
-  constexpr bool EDGES = L == 1;
-  constexpr size_t LDS = wgrad_lds_floats(EDGES ? 5 : 1) * sizeof(float);
-  auto kern = k_conv_wgrad<SRCX, gm.ks, gm.pad, gm.lin, R, gm.pool, gm.lp, kWgradRch, EDGES>;
-  static bool attr = false;
-  if (!attr) {
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)LDS));
-    attr = true;
-  }
-  WgradArgs a = a0;
-  const long rows = (long)a.M * R;
-  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_F32, rows, nchunk);
-  dim3 grid((unsigned)((gm.ks * a.cin + 127) / 128), (unsigned)((a.cout + 127) / 128), (unsigned)nchunk);
-  DCUE_LAUNCH(kern, grid, dim3(256), LDS, s, a);
-  DCUE_LAUNCH_CHECK();
-  return DCUE_OK;
 }
 
 template <int L, int SRCX>
@@ -1997,75 +1437,12 @@ static int wgrad16t_launch(const WgradArgs& a0, int nchunk, hipStream_t s) {
   return DCUE_OK;
 }
 
-static int wgrad1k_launch(const WgradArgs& a0, int nchunk, hipStream_t s) {
-  constexpr LayerGeom gm = layer_geom(1);
-  constexpr int R = gm.lp * gm.pool;
-  constexpr size_t LDS = w1k_lds_bytes<R, gm.ks>();
-  auto kern = k_conv_wgrad1k<gm.ks, gm.pad, gm.lin, R, gm.pool, gm.lp>;
-  if (a0.cin != kMels || a0.cout % 4 || a0.cout > kW1kThreads) return DCUE_ERR_INVALID;
-  static bool attr = false;
-  if (!attr) {
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    attr = true;
-  }
-  WgradArgs a = a0;
-  const long rows = (long)a.M * R;
-  if (rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;  // 32-bit row indices
-  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_1K, rows, nchunk);
-  if (a.rows_per_chunk / R + 3 > kWgItems) return DCUE_ERR_INVALID;  // (wgrad_nchunk keeps it in range)
-  const unsigned tiles = (unsigned)(((a.cout + kW1kO - 1) / kW1kO) * gm.ks);
-  DCUE_LAUNCH(kern, dim3(tiles * (unsigned)nchunk), dim3(kW1kThreads), LDS, s, a);
-  DCUE_LAUNCH_CHECK();
-  return DCUE_OK;
-}
-
-template <int L, int SRCX>
-static int wgrad16_layer(const WgradArgs& a0, int nchunk, hipStream_t s) {
-  constexpr LayerGeom gm = layer_geom(L);
-  constexpr int R = gm.lp * gm.pool;
-  if constexpr (L == 1) {
-    const int kernel = wgrad_kernel(1, a0.cin, a0.cout, SRCX, true);
-    if constexpr (SRCX == SRC_TRACK_F16)
-      if (kernel == WK_1K) return wgrad1k_launch(a0, nchunk, s);
-    if (kernel == WK_16T) return wgrad16t_launch<1, SRCX>(a0, nchunk, s);
-  }
-  auto kern = k_conv_wgrad16<SRCX, gm.ks, gm.pad, gm.lin, R, gm.pool, gm.lp, L == 1>;
-  static bool attr = false;
-  if (!attr) {
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kW16LdsB));
-    attr = true;
-  }
-  WgradArgs a = a0;
-  const long rows = (long)a.M * R;
-  if (rows >= (1L << 30)) return DCUE_ERR_UNSUPPORTED;  // 32-bit row indices
-  a.rows_per_chunk = (int)wgrad_chunk_rows(WK_16, rows, nchunk);
-  dim3 grid((unsigned)((gm.ks * a.cin + 127) / 128), (unsigned)((a.cout + 127) / 128), (unsigned)nchunk);
-  DCUE_LAUNCH(kern, grid, dim3(256), kW16LdsB, s, a);
-  DCUE_LAUNCH_CHECK();
-  return DCUE_OK;
-}
-
-int launch_conv_wgrad(int layer, int src, const WgradArgs& a, int nchunk, hipStream_t s) {
-  if (wgrad_f16_on()) {  // layer 1 reads the track table (bn0 applied at the fill), not xhat0
-    switch (layer) {
-      case 1: return src == SRC_TRACK_F16 ? wgrad16_layer<1, SRC_TRACK_F16>(a, nchunk, s)
-                                          : wgrad16_layer<1, SRC_TRACK_F32>(a, nchunk, s);
-      case 2: return wgrad16_layer<2, SRC_ACT>(a, nchunk, s);
-      case 3: return wgrad16_layer<3, SRC_ACT>(a, nchunk, s);
-      case 4: return wgrad16_layer<4, SRC_ACT>(a, nchunk, s);
-      case 5: return wgrad16_layer<5, SRC_ACT>(a, nchunk, s);
-      default: return DCUE_ERR_INVALID;
-    }
-  }
-  switch (layer) {
-    case 1: (void)src; return conv1_wgrad(a, nchunk, s);  // X = xhat0 (k_xhat0), whatever the table dtype
-    case 2: return wgrad_layer<2, SRC_ACT>(a, nchunk, s);
-    case 3: return wgrad_layer<3, SRC_ACT>(a, nchunk, s);
-    case 4: return wgrad_layer<4, SRC_ACT>(a, nchunk, s);
-    case 5: return wgrad_layer<5, SRC_ACT>(a, nchunk, s);
-    default: return DCUE_ERR_INVALID;
-  }
+// conv 1's weight gradient, the step's tail: split-f16 tap-fused over the track table (`src` its
+// type; bn0 applied at the fill), or f32 MFMA over xhat0 (k_xhat0), whatever the table's type
+int launch_conv_wgrad(int src, const WgradArgs& a, int nchunk, hipStream_t s) {
+  if (!wgrad_f16_on()) return conv1_wgrad(a, nchunk, s);
+  return src == SRC_TRACK_F16 ? wgrad16t_launch<1, SRC_TRACK_F16>(a, nchunk, s)
+                              : wgrad16t_launch<1, SRC_TRACK_F32>(a, nchunk, s);
 }
 
 // Sum partial blocks over chunks and write reference layout dW[o][c][k], db[o]. A workgroup owns
@@ -2154,30 +1531,26 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_multi(WgradMulti w) {
   const WgradArgs& a = w.a[j];
   wgrad_reduce_body(a.wpart, a.bpart, w.nchunk[j], a.cout, a.cin, layer_geom(w.layer[j] == 6 ? 5 : w.layer[j]).ks, 1,
                     w.dW[j], w.db[j], nullptr, nullptr, b - w.rstart[j]);
-  dev_signal_wg(w.done_sig);  // (plans, A/B: the late Adam's relay waits for every workgroup)
 }
 
 int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
   const bool f16 = wgrad_f16_on();
-  const size_t LDS = f16 ? kW16LdsB : wgrad_lds_floats(1) * sizeof(float);
+  const size_t LDS = f16 ? kW16LdsB : kWgradLdsB;
   static bool attr = false;
   if (!attr) {
     DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv_wgrad_multi, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(wgrad_lds_floats(1) * sizeof(float))));
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv_wgrad16_multi<1>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kW16LdsB));
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv_wgrad16_multi<2>,
+                                       (int)kWgradLdsB));
+    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_conv_wgrad16_multi,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kW16LdsB));
     attr = true;
   }
   w.start[0] = 0;
   w.rstart[0] = 0;
   if (w.n < 1 || w.n > kWgradMultiMax) return DCUE_ERR_INVALID;
-  if (w.layer[0] == 2 && wgrad_kernel(2, w.a[0].cin, w.a[0].cout, SRC_ACT, w.n == 1) == WK_16T) {  // layer 2 alone
+  if (w.layer[0] == 2 && wgrad_kernel(2, w.a[0].cin, w.n == 1) == WK_16T) {  // layer 2 alone
     const WgradArgs& a = w.a[0];
     TRY((wgrad16t_launch<2, SRC_ACT>(a, w.nchunk[0], s)));
     w.rstart[1] = wgrad_reduce_blocks(a.cout, a.cin, 4);
-    if (w.done_sig && w.rstart[1] != w.done_blocks) return DCUE_ERR_INVALID;
     DCUE_LAUNCH(k_wgrad_reduce_multi, dim3((unsigned)w.rstart[1]), dim3(256), 0, s, w);
     DCUE_LAUNCH_CHECK();
     return DCUE_OK;
@@ -2195,20 +1568,8 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s) {
     w.start[j + 1] = w.start[j] + w.kt[j] * w.ot[j] * w.nchunk[j];
     w.rstart[j + 1] = w.rstart[j] + wgrad_reduce_blocks(a.cout, a.cin, gm.ks);
   }
-  if (w.done_sig && w.rstart[w.n] != w.done_blocks) return DCUE_ERR_INVALID;
   if (f16)
-  {
-    // two workgroups per CU (the layer-5 / fc branch spills 148 B per lane at that register budget);
-    // DCUE_W16_MULTI_OCC=1: one, no spill (A/B diagnostic)
-    static const bool occ1 = [] {
-      const char* e = getenv("DCUE_W16_MULTI_OCC");
-      return e && e[0] == '1';
-    }();
-    if (occ1)
-      DCUE_LAUNCH(k_conv_wgrad16_multi<1>, dim3((unsigned)w.start[w.n]), dim3(256), LDS, s, w);
-    else
-      DCUE_LAUNCH(k_conv_wgrad16_multi<2>, dim3((unsigned)w.start[w.n]), dim3(256), LDS, s, w);
-  }
+    DCUE_LAUNCH(k_conv_wgrad16_multi, dim3((unsigned)w.start[w.n]), dim3(256), LDS, s, w);
   else
     DCUE_LAUNCH(k_conv_wgrad_multi, dim3((unsigned)w.start[w.n]), dim3(256), LDS, s, w);
   DCUE_LAUNCH_CHECK();

@@ -180,11 +180,6 @@ struct WgradMulti {
   int kt[kWgradMultiMax], ot[kWgradMultiMax];  // kc / o tiles per layer
   int start[kWgradMultiMax + 1];      // wgrad block ranges
   int rstart[kWgradMultiMax + 1];     // reduce block ranges
-  // plans (DCUE_LATE_SIG_WG=1, A/B): every workgroup of the reduce adds 1 once its sums are stored
-  // (dev_signal_wg); done_blocks: the reduce's grid as the host counted it into the word's issue
-  // counter (wgrad_reduce_blocks per slot) -- a launch whose grid differs is refused
-  unsigned* done_sig;
-  int done_blocks;
 };
 // workgroups of one slot's part of k_wgrad_reduce_multi (ks: the layer's taps; the fc slot: 1)
 inline int wgrad_reduce_blocks(int cout, int cin, int ks) {
@@ -194,19 +189,16 @@ int launch_conv_wgrad_multi(WgradMulti w, hipStream_t s);
 // the weight-gradient kernels (conv_wgrad.hip wgrad_kernel; dcue_debug_launch_shape reports the number)
 enum {
   WK_16T = 0,        // k_conv_wgrad16t: tap-fused split-f16 (layers 1, 2 with 128 input channels)
-  WK_16 = 1,         // k_conv_wgrad16: kc-tiled split-f16, one layer per launch
-  WK_F32 = 2,        // k_conv_wgrad: f32 MFMA, one layer per launch
   WK_CONV1 = 3,      // k_conv1_wgrad: conv 1 on f32 MFMA over xhat0
   WK_MULTI_F16 = 4,  // k_conv_wgrad16_multi: the multi-layer launch, kc-tiled split-f16
-  WK_MULTI_F32 = 5,  // k_conv_wgrad_multi: the multi-layer launch, f32 MFMA
-  WK_1K = 6          // k_conv_wgrad1k: conv 1, one tap per workgroup (DCUE_W1K=1)
+  WK_MULTI_F32 = 5   // k_conv_wgrad_multi: the multi-layer launch, f32 MFMA
 };
-int wgrad_kernel(int layer, int cin, int cout, int src, bool alone);
+int wgrad_kernel(int layer, int cin, bool alone);
 // dcue_debug_launch_shape's records (include/dcue.h): 5 words per k_conv_rows launch, 4 per weight
 // gradient, 5 for the score / item-gradient tail
 void conv_fwd_shape(int layer, int kc, int nout, int M, int32_t* out);
 void conv_dgrad_shape(int layer, int kc, int nout, int M, int32_t* out);
-void wgrad_shape(int layer, int M, int cout, int cin, int src, bool alone, int32_t* out);
+void wgrad_shape(int layer, int M, int cout, int cin, bool alone, int32_t* out);
 void tail_shape(int n_neg, int n_items, int d, bool gather, bool copy_lists, bool fc, int32_t* out);
 // weight gradients on split-f16 MFMA (DCUE_WGRAD_F16=0: the f32-MFMA kernels)
 bool wgrad_f16_on();
@@ -216,7 +208,8 @@ int launch_conv_dgrad(int layer, int kc, const RowsArgs& a, hipStream_t s);
 // workgroups of that launch over M items (each adds 1 to RowsArgs::done_sig)
 long conv_dgrad_blocks(int layer, int kc, int nout, int M);
 long conv_fwd_blocks(int layer, int kc, int nout, int M);
-int launch_conv_wgrad(int layer, int src, const WgradArgs& a, int nchunk, hipStream_t s);
+// conv 1's weight gradient (`src`: its track table's type)
+int launch_conv_wgrad(int src, const WgradArgs& a, int nchunk, hipStream_t s);
 // xhat0[i][t + 2][c] = (x[track_i][t][c] - mean0[c]) * invstd0[c] in a [M][kXp][128] zero-padded
 // layout, bn0's batch statistics finalized from its accumulators (layer 1's wgrad reads it from `xsrc`)
 int launch_xhat0(int src, const void* tracks, const int32_t* item_track, int M, const unsigned long long* acc0,
@@ -453,10 +446,7 @@ int launch_emb_grad(const float* de, const int64_t* users, int B, int E, float s
 // the next training forward of conv 2 (RowsArgs::rp): the split plans' late Adam, which may run
 // beside the caller stream's dgrad of conv 2 that reads them
 int launch_adam(const dcue_model* m, const dcue_adam_args* a, const int64_t* poff, hipStream_t s,
-                bool flush_slice = true, long dense_lo = 0, long dense_hi = -1, bool defer_dgrad2 = false,
-                unsigned* sig = nullptr);
-// workgroups of the dense Adam sweep over len floats (each adds 1 to launch_adam's sig)
-long adam_dense_blocks(long len);
+                bool flush_slice = true, long dense_lo = 0, long dense_hi = -1, bool defer_dgrad2 = false);
 // conv layer l's packed copies (adam.hip pack_args)
 PackSeg pack_seg(const dcue_model* m, const int64_t* poff, int l);
 int launch_emb_flush_rows(const dcue_model* m, int step, hipStream_t s);
@@ -552,7 +542,7 @@ std::vector<CapturedTimer> timer_take_captured();
 // device, so they take a device-scope release: the default system-scope one writes back and
 // invalidates the caches when the event completes, which measured 4-9 us of idle on the waiting and
 // the recording stream after every event-bound kernel of a step (profiles/r03: the critical
-// chain's gaps). DCUE_EVENT_SCOPE=system restores the default (A/B).
+// chain's gaps).
 unsigned sync_event_flags();
 // side streams (capi.hip): three per device, plus a ring of fork/join events
 struct SidePool {
@@ -690,9 +680,6 @@ struct StepOpts {
   // tower -- same stream order relative to every Adam step, but off the next step's user-tower path
   bool defer_flush_slice = false;
   int flush_slice_step = -1;
-  // the slice issued off the user stream (DCUE_SLICE_STREAM): its end, which the backward's
-  // user-table Adam waits for (written by the forward's user part, read by the backward's)
-  hipEvent_t* slice_done = nullptr;
   // prepared one step ahead from the announced next batch (plans, dcue_plan_set_next): bn0's batch
   // sums already in `acc`, and the conv-1 weight gradient's X operand (k_xhat0) already built
   bool input_stats_done = false;

@@ -182,18 +182,12 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   // issued on the side-issue thread (side.hip) when it runs. The caller's stream waits for them
   // (inputs_ready) inside this step's backward, just before the conv-1 weight gradient -- long after
   // they finished -- so the next launch's conv 1 is ordered after them.
-  // DCUE_INPUTS_WAIT=start waits at the next launch's start instead, =0 not at all (A/B only).
   // DCUE_AHEAD_AT=fork: the lookahead at the backward's first dgrad fork point instead of right
   // behind the prologue (A/B).
-  static const int inputs_wait = [] {
-    const char* e = getenv("DCUE_INPUTS_WAIT");
-    return !e ? 1 : e[0] == '0' ? 0 : e[0] == 's' ? 2 : 1;
-  }();
   static const bool ahead_at_fork = [] {
     const char* e = getenv("DCUE_AHEAD_AT");
     return e && e[0] == 'f';
   }();
-  if (p->inputs_ready && inputs_wait == 2) TRY(wait_point(s, p->inputs_ready));
   p->ahead_items[nxt] = nullptr;
   const bool look = p->next_items && p->xh[nxt];
   if (look) p->ahead_items[nxt] = p->next_items;
@@ -201,7 +195,7 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   p->inputs_ready = ring_event(sp);  // slot nxt's inputs, for the next launch (recorded below)
   // the lookahead, then the inputs_ready record, on wgrad stream 0 after `after`
   DevWait in_sig{};
-  if (dev && inputs_wait == 1) in_sig = DevWait{p->sig + kSigInputs, ++p->sig_issued[kSigInputs], user_fwd_fail_flag()};
+  if (dev) in_sig = DevWait{p->sig + kSigInputs, ++p->sig_issued[kSigInputs], user_fwd_fail_flag()};
   const std::function<int(hipEvent_t)> lookahead = [p, sa, nxt, look, ir = p->inputs_ready, in_sig](hipEvent_t after) -> int {
     if (look) {
       if (after) TRY(wait_point(sa, after));
@@ -249,8 +243,6 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   const bool deferred = p->model.emb_step != nullptr;
   o.flush_slice_step = deferred ? p->pending_flush : -1;
   o.defer_flush_slice = deferred && emb_adam != nullptr;
-  hipEvent_t slice_done = nullptr;
-  o.slice_done = &slice_done;
   // DCUE_SCORE_FORK=1: the score kernel binds a fork point that the user tower's backward waits for
   // (A/B; default: it waits for the dgrad chain's first fork point, one bound event fewer)
   static const bool score_fork = [] {
@@ -303,13 +295,9 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   // then issues first
   if (!prologue_first) TRY(post_prologue());
   if (ahead_at_fork) o.ahead = &lookahead;
-  if (inputs_wait == 1) {
-    o.wait_inputs = p->inputs_ready;
-    o.wait_inputs_seq = iseq;
-    p->inputs_ready = nullptr;
-  } else if (!ahead_at_fork) {
-    TRY(side.wait(iseq));
-  }
+  o.wait_inputs = p->inputs_ready;
+  o.wait_inputs_seq = iseq;
+  p->inputs_ready = nullptr;
   TRY(backward_impl(&p->model, &b, &p->tracks, p->ws, p->ws_bytes, nullptr, p->cfg.emb_grad_scale, o, s));
   HPROF("plan:5");
   p->pending_flush = o.defer_flush_slice ? emb_adam->step : -1;
@@ -318,25 +306,6 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   p->last_stream = s;
   ++p->launches;
   return DCUE_OK;
-}
-
-// DCUE_SPLIT_COMM=0: data-parallel plan steps keep the unsplit exchange (both buckets, then the whole
-// dense Adam on the caller's stream) -- the A/B of comm_exchange_split
-bool split_comm_on() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_SPLIT_COMM");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-// DCUE_SPLIT_ADAM=0 keeps the whole dense Adam on the caller's stream after the join (A/B)
-bool split_adam_on() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_SPLIT_ADAM");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 int capture(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t, void* ws, size_t ws_bytes,
@@ -524,26 +493,12 @@ extern "C" int dcue_plan_step(dcue_plan* p, const int64_t* users_src, const int3
   dcue_adam_args emb = *adam, dense = *adam;
   emb.parts = DCUE_ADAM_EMBEDDING;
   dense.parts = DCUE_ADAM_DENSE;
-  if (split_adam_on() && (!p->comm || split_comm_on())) {
-    // the dense Adam split over two streams (StepOpts); with a communicator each part after its own
-    // bucket's all-reduce (comm_exchange_split), the divide by the world size fused into the sweep
-    if (p->comm) dense.grad_div = p->comm_world;
-    TRY(issue_eager(p, users_src, item_track_src, (hipStream_t)stream, &emb, &dense));
-    HPROF("plan_step:issue");
-    return DCUE_OK;
-  }
-  const int st = issue_eager(p, users_src, item_track_src, (hipStream_t)stream, &emb);
-  if (st) return st;
+  // the dense Adam split over two streams (StepOpts); with a communicator each part after its own
+  // bucket's all-reduce (comm_exchange_split), the divide by the world size fused into the sweep
+  if (p->comm) dense.grad_div = p->comm_world;
+  TRY(issue_eager(p, users_src, item_track_src, (hipStream_t)stream, &emb, &dense));
   HPROF("plan_step:issue");
-  if (p->comm) {  // the DDP mean of the dense gradient: RCCL sum here, the divide inside Adam
-    TRY(dcue::comm_exchange_step(p->comm, p->model.grads, p->late, p->n_dense, p->tails[1],
-                                 (hipStream_t)stream));
-    dense.grad_div = p->comm_world;
-    HPROF("plan_step:exchange");
-  }
-  const int r = dcue_adam_step(&p->model, &dense, stream);
-  HPROF("plan_step:adam");
-  return r;
+  return DCUE_OK;
 }
 
 extern "C" int dcue_plan_set_comm(dcue_plan* p, dcue_comm* comm) {

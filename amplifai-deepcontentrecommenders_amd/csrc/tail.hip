@@ -926,23 +926,12 @@ static bool item_grad_multi_wg(bool gather, bool copy_lists, bool fc, int d) {
   return (!gather || copy_lists) && (!fc || d <= 128);
 }
 // W staged in LDS (64 KB per workgroup at d = 128), or read from L2 in the g5 loop
-// (DCUE_ITEMGRAD_WLDS=0: A/B diagnostic)
 static bool item_grad_wlds(bool multi, bool fc, int d) {
-  static const bool wlds_on = [] {
-    const char* e = getenv("DCUE_ITEMGRAD_WLDS");
-    return !(e && e[0] == '0');
-  }();
-  return multi ? fc && d % 4 == 0 && wlds_on : fc && d <= kItemGradWLds && d % 4 == 0;
+  return fc && d % 4 == 0 && (multi || d <= kItemGradWLds);
 }
 // items per workgroup of k_item_grad_multi: many items (catalogue M = B(1+N)): 16; a few hundred: 4;
 // in-batch M = B = 64: one item per workgroup (measured GPU-only, A/B: 3 us under four per workgroup)
-// (DCUE_ITEMGRAD_IT = 1, 2, 4 or 16 forces one: A/B diagnostic)
 static int item_grad_it(int n_items) {
-  static const int forced = [] {
-    const char* e = getenv("DCUE_ITEMGRAD_IT");
-    return e ? atoi(e) : 0;
-  }();
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 16) return forced;
   return n_items >= 512 ? 16 : n_items >= 256 ? 4 : 1;
 }
 

@@ -636,10 +636,6 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
     const char* e = getenv("DCUE_TEXT_PARTS");
     return e ? atoi(e) : 1;
   }();
-  static const int xcds_env = [] {
-    const char* e = getenv("DCUE_TEXT_XCDS");
-    return e ? atoi(e) : 4;
-  }();
   static const int bpd_env = [] {  // (A/B: the config-4 kernel's weight-prefetch depth, 6 / 10 / 15 steps)
     const char* e = getenv("DCUE_TEXT_BPD");
     return e ? atoi(e) : 6;
@@ -654,9 +650,9 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
     int wv = shape / 10, nct = shape % 10;
     if (tb.C % (16 * wv * nct) || wv > 8) wv = tb.C % 128 == 0 ? 8 : 4, nct = 1;
     // work units on 4 XCDs while they fill at most 4 x 32 CUs at one workgroup per CU (the weight
-    // operand's per-XCD L2 fills halve); DCUE_TEXT_XCDS=8 spreads them over all eight
+    // operand's per-XCD L2 fills halve); more units spread over all eight
     const long nunit = (long)M * (tb.C / (16 * wv * nct)) * spl;
-    a.nxcd = xcds_env == 8 || nunit > 4 * 32 ? 8 : 4;
+    a.nxcd = nunit > 4 * 32 ? 8 : 4;
     const unsigned grid = (unsigned)((nunit + a.nxcd - 1) / a.nxcd * 8);
     auto pick = [&](auto kern) -> int {
       static bool attr = false;  // (one per instantiation)
@@ -714,13 +710,7 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
 // item chunks of the text weight gradient: one up to 128 items (the in-batch shapes: no partials),
 // else about 128 items per chunk, at most 16 chunks
 int text_wgrad_nchunk(int M) {
-  // DCUE_TEXT_WGRAD_ITEMS: items per chunk (A/B diagnostic; default 128)
-  static const int per = [] {
-    const char* e = getenv("DCUE_TEXT_WGRAD_ITEMS");
-    const int v = e ? atoi(e) : 0;
-    return v >= 8 && v <= 4096 ? v : 128;
-  }();
-  const int n = (M + per - 1) / per;
+  const int n = (M + 127) / 128;
   return n < 1 ? 1 : (n > 16 ? 16 : n);
 }
 

@@ -462,7 +462,7 @@ def workspace_bytes(dims, max_rows, max_neg, max_items):
 
 
 LAUNCH_SHAPE_WORDS = 74  # DCUE_LAUNCH_SHAPE_WORDS
-WGRAD_KERNELS = ("wgrad16t", "wgrad16", "wgrad_f32", "conv1_wgrad", "multi_f16", "multi_f32", "wgrad1k")
+WGRAD_KERNELS = {0: "wgrad16t", 3: "conv1_wgrad", 4: "multi_f16", 5: "multi_f32"}  # by WK_* code
 
 
 def launch_shape(dims, layout, B, N, M):

@@ -12,7 +12,7 @@ LDS_BYTES = 160 * 1024            # gfx950 LDS per workgroup
 CHAN_LDS = (5 * 256 + 4) * 4      # conv_rows.h ChanLds, static LDS beside the slab
 # (ks, pad, pool, Lin, Lp) per conv layer (dcue_common.h layer_geom; oracle CONV_SPECS)
 GEOM = {1: (4, 2, 4, 131, 33), 2: (4, 2, 4, 33, 8), 3: (4, 2, 4, 8, 2), 4: (2, 1, 2, 2, 1), 5: (1, 0, 1, 1, 1)}
-F16_KERNELS = ("wgrad16t", "wgrad16", "multi_f16", "wgrad1k")
+F16_KERNELS = ("wgrad16t", "multi_f16")
 K_WG_ITEMS = 128                  # conv_wgrad.hip kWgItems: the tap-fused conv-1 kernel's LDS item table
 
 
@@ -57,7 +57,7 @@ def test_planner_invariants(nat, H, d):
                     assert rpc % 64 == 0, (where, l, rpc)
                 if kernel == "conv1_wgrad":
                     assert rpc % pool == 0, (where, l, rpc)
-                if l == 1 and kernel in ("wgrad16t", "wgrad1k"):
+                if l == 1 and kernel == "wgrad16t":
                     assert rpc // 132 + 3 <= K_WG_ITEMS, (where, rpc)
             cpw, kernel, it, wlds, last = s["tail"]
             assert cpw in (0, 4, 8) and it in (1, 2, 4, 16) and 1 <= last <= it and (M - last) % it == 0, where
