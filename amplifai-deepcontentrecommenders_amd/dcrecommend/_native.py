@@ -119,6 +119,12 @@ class LogmelConfig(ctypes.Structure):
                 ("log_scale", ctypes.c_float)]
 
 
+class ResampleConfig(ctypes.Structure):
+    """dcue_resample_config (sample-rate conversion, added under ABI 17)."""
+    _fields_ = [("rate_in", ctypes.c_int32), ("rate_out", ctypes.c_int32), ("zeros", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("beta", ctypes.c_double), ("rolloff", ctypes.c_double)]
+
+
 class TrackStore(ctypes.Structure):
     """dcue_track_store (full-length tracks for dcue_crop_tracks, added under ABI 17)."""
     _fields_ = [("data", ctypes.c_void_p), ("frame_ptr", ctypes.c_void_p), ("n_tracks", ctypes.c_int64),
@@ -138,6 +144,9 @@ LOGMEL_POWER, LOGMEL_DB, LOGMEL_LOG1P = 0, 1, 2  # DCUE_LOGMEL_*
 LOGMEL_MODES = {"power": LOGMEL_POWER, "db": LOGMEL_DB, "log1p": LOGMEL_LOG1P}
 LOGMEL_FLAG_NONFINITE = 1
 LOGMEL_N_FFT = (256, 512, 1024, 2048)
+# (zeros, beta, rolloff): the published constants of resampy's kaiser_best / kaiser_fast windows
+RESAMPLE_QUALITIES = {"best": (64, 14.769656459379492, 0.9475937167399596), "fast": (16, 8.555504641634386, 0.85)}
+RESAMPLE_MAX_TABLE_BYTES = 16 << 20  # DCUE_RESAMPLE_MAX_TABLE_BYTES
 FOLDIN_MAX_STEPS, FOLDIN_MAX_NEG, FOLDIN_MAX_POS = 4096, 256, 1024
 FOLDIN_EMPTY, FOLDIN_NONFINITE, FOLDIN_DROPPED = 1, 2, 4  # out_flags bits
 MT_STATE_BYTES = 624 * 4 + 16
@@ -270,6 +279,13 @@ _SIGS = {
     "dcue_logmel_table_init": ([ctypes.POINTER(LogmelConfig), _P, ctypes.c_size_t, _P], ctypes.c_int),
     "dcue_logmel": ([ctypes.POINTER(LogmelConfig), _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                      ctypes.c_int32, _P, _P, _P], ctypes.c_int),
+    "dcue_resample_length": ([ctypes.POINTER(ResampleConfig), ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+                             ctypes.c_int),
+    "dcue_resample_table_bytes": ([ctypes.POINTER(ResampleConfig), ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_resample_table_fill_host": ([ctypes.POINTER(ResampleConfig), _P, ctypes.c_size_t], ctypes.c_int),
+    "dcue_resample_table_init": ([ctypes.POINTER(ResampleConfig), _P, ctypes.c_size_t, _P], ctypes.c_int),
+    "dcue_resample": ([ctypes.POINTER(ResampleConfig), _P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                       ctypes.c_int64, _P, _P], ctypes.c_int),
     "dcue_crop_tracks": ([ctypes.POINTER(TrackStore), ctypes.POINTER(CropConfig), _P, ctypes.c_int64, _P,
                           ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     "dcue_crop_starts_host": ([ctypes.POINTER(CropConfig), _P, _P, ctypes.c_int64, _P], ctypes.c_int),
@@ -316,7 +332,7 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
-        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop")):  # the calls that leave a dcue_last_error text
+        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_resample")):  # the calls that leave a dcue_last_error text
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 

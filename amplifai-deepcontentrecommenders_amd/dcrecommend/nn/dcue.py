@@ -675,9 +675,10 @@ class DCUE(Trainer):
         return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
 
     # ------------------------------------------------------------------ unseen songs
-    def embed_audio(self, wave, logmel=None, frame0=0, crops=None):
+    def embed_audio(self, wave, logmel=None, frame0=0, crops=None, sample_rate=None, resample="best"):
         """[n, d] item factors of waveforms ([n_samples] or [n, n_samples], mono, at the front end's
-        sample rate) -- the cold-start step for a song nobody has played: audio.LogMel.track_rows writes
+        sample rate, or at sample_rate when one is given: the clips are then resampled on the GPU first,
+        audio.Resampler with quality `resample`, and frame0 counts frames of the resampled clip) -- the cold-start step for a song nobody has played: audio.LogMel.track_rows writes
         a temporary fp16 track table on the GPU (frames frame0 .. frame0 + 130 of each clip) and
         dcue_item_tower_eval reads it where it lies. Needs no dataset and no host copy. logmel: an
         audio.LogMel (default: one with the default configuration, kept for later calls). A clip with a
@@ -698,6 +699,8 @@ class DCUE(Trainer):
         self.model.eval()
         self.model._require_device()
         ds = nat.storage_dims(self.model._flat["dims"]).feature_dim
+        if sample_rate is not None:
+            wave = logmel._at_rate(wave, sample_rate, resample)
         if crops is None:
             return self._tower_over(logmel.track_rows(wave, frame0, torch.float16), ds)[:, :self.feature_dim].contiguous()
         crops = int(crops)
@@ -732,23 +735,23 @@ class DCUE(Trainer):
                       "dcue_item_tower_eval")
         return feat[:n]
 
-    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None, crops=None):
+    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None, crops=None, sample_rate=None, resample="best"):
         """The k catalogue songs nearest to each clip, by the cosine of its embed_audio factor to the
         item factors: one list of (song_id, score) pairs per clip, as similar_songs returns (nothing is
         excluded: the clip is not in the catalogue). crops: as embed_audio -- the whole song, not its
-        first window."""
+        first window. sample_rate / resample: as embed_audio."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
-        q = self.embed_audio(wave, logmel, crops=crops)
+        q = self.embed_audio(wave, logmel, crops=crops, sample_rate=sample_rate, resample=resample)
         out = self._topk("audio", ds, False).topk(q, self._item_feat_by_index(), np.arange(q.shape[0]), k)
         return self._as_pairs(ds, *out)
 
-    def listeners_for_audio(self, wave, k=10, logmel=None, crops=None):
+    def listeners_for_audio(self, wave, k=10, logmel=None, crops=None, sample_rate=None, resample="best"):
         """The k users with the highest cosine to each clip -- "who should hear this": the clips'
         embed_audio factors against user_factors on the same kernel. One list of (user_id, score) pairs
-        per clip, best first. crops: as embed_audio."""
+        per clip, best first. crops, sample_rate, resample: as embed_audio."""
         self._require_factors()
-        q = self.embed_audio(wave, logmel, crops=crops)
+        q = self.embed_audio(wave, logmel, crops=crops, sample_rate=sample_rate, resample=resample)
         key = ("topk", "listeners")
         if key not in self._evals:
             self._evals[key] = rank.TopK(None, None, None, self.device, n_cand=int(self.user_factors.shape[0]))

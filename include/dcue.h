@@ -866,7 +866,7 @@ int dcue_list_ild_mean(const double* ild, const int32_t* flags, int32_t n_lists,
  * Compression. DCUE_LOGMEL_POWER: P. DCUE_LOGMEL_DB: 10 log10(max(P, amin)) (ref = 1.0); P <= amin gives
  *   the floor 10 log10(amin), rounded once from double. DCUE_LOGMEL_LOG1P: log(1 + log_scale sqrt(P)).
  *   Computed in f32; out_dtype 0 converts to fp16 last (round to nearest even).
- * wave [n_clips][n_samples] f32, already at sample_rate. out [n_clips][n_frames][128] of out_dtype: the
+ * wave [n_clips][n_samples] f32, already at sample_rate (dcue_resample, below, brings it there). out [n_clips][n_frames][128] of out_dtype: the
  *   dcue_tracks layout, so with n_frames = DCUE_N_FRAMES `out` is a track table as it stands. The call
  *   writes frames frame0 .. frame0 + n_frames - 1 of each clip. flags [n_clips] is zeroed by the call;
  *   bit 0 (DCUE_LOGMEL_FLAG_NONFINITE) is set for a clip when a sample the requested frames read is NaN
@@ -903,6 +903,54 @@ int dcue_logmel_table_fill_host(const dcue_logmel_config* cfg, void* table_host,
 int dcue_logmel_table_init(const dcue_logmel_config* cfg, void* table_dev, size_t bytes, void* stream);
 int dcue_logmel(const dcue_logmel_config* cfg, const void* table_dev, const float* wave, int64_t n_clips,
                 int64_t n_samples, int64_t frame0, int32_t n_frames, void* out, int32_t* flags, void* stream);
+
+/* ------------------------------------------- sample-rate conversion ahead of it (added under ABI 17) */
+/* Music is distributed at 44.1 or 48 kHz and the model reads 22,050 Hz: dcue_resample converts mono f32
+ * waveforms from rate_in to rate_out in one launch, no workspace. The reference has no counterpart; the
+ * definition is this project's own, pinned by tests/resample_reference.py.
+ * Definition. A rational polyphase resampler with a Kaiser-windowed sinc evaluated exactly per phase (no
+ *   interpolated filter table). g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g,
+ *   s = rolloff min(1, L / M), Kh = ceil(zeros / s), K = 2 Kh taps per output, n_out = ceil(n_in L / M).
+ *   Output m: q = floor(m M / L), p = (m M) mod L,
+ *     y[m] = sum_{k=0..K-1} tab[p][k] x[q - Kh + 1 + k],   x = 0 outside [0, n_in),
+ *     tab[p][k] = s sinc(u) w(u),  u = s (p / L - (k - Kh + 1)),  sinc(u) = sin(pi u) / (pi u),
+ *     w(u) = I0(beta sqrt(1 - (u / zeros)^2)) / I0(beta) for |u| < zeros, 0 otherwise.
+ *   Two named qualities carry the published constants of resampy's kaiser_best / kaiser_fast windows:
+ *   best = {zeros 64, beta 14.769656459379492, rolloff 0.9475937167399596}, fast = {16, 8.555504641634386,
+ *   0.85}; parity with resampy itself (which interpolates a sampled filter) is not claimed.
+ * Summation order. y[m] is the chain acc = fmaf(tab[p][k], x[q - Kh + 1 + k], acc) over k = 0 .. K-1 in
+ *   ascending order from acc = +0: exact products, one rounding per addition. An output's bits are a
+ *   function of its K samples and its phase row alone -- not of n_clips, of out0 / n_out, of the clip's
+ *   place in the batch or of what shares the launch.
+ * wave [n_clips][n_in] f32. out [n_clips][n_out] f32 holds outputs out0 .. out0 + n_out - 1 of each clip.
+ *   There is no flag word: a NaN or infinite sample propagates by IEEE rules into exactly the outputs whose
+ *   K samples include it (dcue_logmel's flag then names the clip); other outputs and clips keep their bits.
+ * Table. dcue_resample_table_bytes bytes of device memory, filled once per configuration by
+ *   dcue_resample_table_init (which synchronises `stream`): int32 header[8] {magic, L, M, K, Kh, zeros,
+ *   rate_in, rate_out}, then f32 tab[L][K]. dcue_resample_table_fill_host writes the same bytes to host
+ *   memory: every tap computed in double precision (I0 by its power series) and rounded once, so the
+ *   kernel calls no device transcendental. dcue_resample must be given the table of the same
+ *   configuration; the kernel compares the header with its own L, M, K, Kh and, where they differ, writes
+ *   NaN to every output of the call instead of reading taps that are not there.
+ * Every call validates on the host before its first device call, so the refusals below are reachable
+ * without a GPU, each with a dcue_last_error text. DCUE_ERR_INVALID: a rate < 1; equal rates (nothing to
+ * resample); zeros < 1; rolloff outside (0, 1]; beta < 0; a negative count; an output range that reaches
+ * past n_out(n_in); a null pointer; a table size other than dcue_resample_table_bytes. DCUE_ERR_UNSUPPORTED:
+ * a table larger than DCUE_RESAMPLE_MAX_TABLE_BYTES (32000 -> 22050 `best` is 341 KB; near-coprime rates
+ * such as 44100 -> 44101 are refused rather than served slowly); n_in beyond 2^31 - 1; n_clips x output
+ * tiles beyond the grid limit. n_clips == 0 or n_out == 0 is DCUE_OK with no launch. dcue_resample is
+ * asynchronous on `stream`. */
+#define DCUE_RESAMPLE_MAX_TABLE_BYTES (16 << 20)
+typedef struct dcue_resample_config {
+  int32_t rate_in, rate_out, zeros, reserved;
+  double beta, rolloff;
+} dcue_resample_config;
+int dcue_resample_length(const dcue_resample_config* cfg, int64_t n_in, int64_t* n_out_host);
+int dcue_resample_table_bytes(const dcue_resample_config* cfg, size_t* bytes_host);
+int dcue_resample_table_fill_host(const dcue_resample_config* cfg, void* table_host, size_t bytes);
+int dcue_resample_table_init(const dcue_resample_config* cfg, void* table_dev, size_t bytes, void* stream);
+int dcue_resample(const dcue_resample_config* cfg, const void* table_dev, const float* wave,
+                  int64_t n_clips, int64_t n_in, int64_t out0, int64_t n_out, float* out, void* stream);
 
 /* ----------------------------------- window crops of full-length tracks (added under ABI 17) */
 /* The reference trains on a different DCUE_N_FRAMES-frame window of a song every time it loads the song

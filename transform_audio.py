@@ -6,10 +6,13 @@ MI355X build, on the GPU (dcrecommend.audio.LogMel, include/dcue.h dcue_logmel):
 
   python transform_audio.py --wav-dir clips/ --out-dir mels/ --metadata metadata.csv
   python transform_audio.py ... --n-fft 2048 --hop 512 --compress log1p --top-db 80
+  python transform_audio.py ... --resample best      # 44.1 / 48 kHz files in, 22,050 Hz spectrograms out
 
-Every *.wav under --wav-dir (16-bit PCM, mono or stereo, already at --sample-rate: resampling is out of
-scope and a different rate is an error) becomes one torch.save'd float32 [128, T] tensor in --out-dir,
-T = 1 + n_samples // hop frames. Files of equal length go through the GPU together, --batch at a time.
+Every *.wav under --wav-dir (16-bit PCM, mono or stereo) becomes one torch.save'd float32 [128, T] tensor
+in --out-dir, T = 1 + n_samples // hop frames of the clip at --sample-rate. A file at another rate is an
+error with --resample off (the default); with best or fast it is resampled on the GPU first
+(dcrecommend.audio.Resampler, include/dcue.h dcue_resample). Files of equal rate and length go through
+the GPU together, --batch at a time.
 The CSV has the columns idx, song_id, data_mel -- song_id (the file's name without .wav) in column 1 and
 the tensor's path in `data_mel`, as datasets/dcueitemset.py reads them. The item tower takes 131
 frames: 66,560 samples (3.02 s) at the defaults.
@@ -40,7 +43,9 @@ def parse(argv=None):
     ap.add_argument("--amin", type=float, default=1e-10)
     ap.add_argument("--log-scale", type=float, default=10.0)
     ap.add_argument("--top-db", type=float, default=None)
-    ap.add_argument("--batch", type=int, default=256, help="clips of one length per GPU call")
+    ap.add_argument("--resample", choices=["off", "best", "fast"], default="off",
+                    help="resample files at another rate on the GPU (off: such a file is an error)")
+    ap.add_argument("--batch", type=int, default=256, help="clips of one rate and length per GPU call")
     ap.add_argument("--device", default="cuda:0")
     return ap.parse_args(argv)
 
@@ -56,15 +61,20 @@ def main(argv=None):
                       device=args.device)
     os.makedirs(args.out_dir, exist_ok=True)
     by_length = {}
-    for name in names:  # files of equal length share a launch
-        x, _ = audio.read_wav(os.path.join(args.wav_dir, name), sample_rate=args.sample_rate)
-        by_length.setdefault(len(x), []).append((name, x))
+    for name in names:  # files of equal rate and length share a launch
+        x, rate = audio.read_wav(os.path.join(args.wav_dir, name),
+                                 sample_rate=args.sample_rate if args.resample == "off" else None)
+        by_length.setdefault((rate, len(x)), []).append((name, x))
     paths = {}
-    for length, clips in sorted(by_length.items()):
+    for (rate, length), clips in sorted(by_length.items()):
         for s in range(0, len(clips), args.batch):
             part = clips[s:s + args.batch]
             try:
-                mel = lm.reference_tensor(np.stack([x for _, x in part])).cpu()
+                wave = np.stack([x for _, x in part])
+                if rate == args.sample_rate:
+                    mel = lm.reference_tensor(wave).cpu()
+                else:
+                    mel = lm.reference_tensor(wave, source_rate=rate, resample=args.resample).cpu()
             except ValueError as e:
                 raise SystemExit("transform_audio: %s (%d-sample files %s ...)" % (e, length, part[0][0]))
             for (name, _), m in zip(part, mel):
@@ -75,7 +85,7 @@ def main(argv=None):
         w.writerow(["idx", "song_id", "data_mel"])
         for i, name in enumerate(names):
             w.writerow([i, name[:-4], paths[name]])
-    print("transform_audio: %d files, %d lengths -> %s" % (len(names), len(by_length), args.metadata))
+    print("transform_audio: %d files, %d (rate, length) groups -> %s" % (len(names), len(by_length), args.metadata))
     return 0
 
 
