@@ -705,6 +705,23 @@ int dcue_debug_launch_shape(const dcue_dims* dims, int32_t layout, int32_t B, in
   return DCUE_OK;
 }
 
+int dcue_debug_text_shape(const dcue_dims* dims, int32_t M, int32_t* out_host, int32_t cap) {
+  TRY(check_dims(dims));
+  if (!tower_text(dims) || !out_host || cap < DCUE_TEXT_SHAPE_WORDS || M <= 0) return DCUE_ERR_INVALID;
+  // the arguments text_branch gives the launchers, the knobs at their defaults
+  const TextFwdShape f = text_fwd_shape(M, dims->text_len, st_word(dims), st_text(dims), false, 81, 1, true, 6);
+  if (!f.valid) return DCUE_ERR_INVALID;
+  const TextWgradShape g = text_wgrad_shape(M);
+  int32_t* o = out_host;
+  o[0] = f.full ? 0 : 1;
+  o[1] = f.tb; o[2] = f.wv; o[3] = f.nct; o[4] = f.full ? f.bpd : 0; o[5] = f.nch;
+  o[6] = f.full ? f.nxcd : 0;
+  o[7] = (int32_t)f.nunit; o[8] = (int32_t)f.grid;
+  o[9] = (int32_t)f.lds; o[10] = (int32_t)f.lds_static; o[11] = f.last;
+  o[12] = g.nchunk; o[13] = g.items_per_chunk; o[14] = g.last; o[15] = g.reduce ? 1 : 0;
+  return DCUE_OK;
+}
+
 int dcue_workspace_outputs(const dcue_dims* dims, int32_t B, int32_t N, int32_t M,
                            size_t* offsets_host) {
   TRY(check_dims(dims));
@@ -728,6 +745,17 @@ int dcue_workspace_activations(const dcue_dims* dims, int32_t B, int32_t N, int3
     offsets_host[2 * (l - 1)] = (size_t)w.y[l];
     offsets_host[2 * (l - 1) + 1] = (size_t)w.idx[l];
   }
+  return DCUE_OK;
+}
+
+int dcue_workspace_text(const dcue_dims* dims, int32_t B, int32_t N, int32_t M, size_t* offsets_host) {
+  TRY(check_dims(dims));
+  if (!tower_text(dims) || !offsets_host || B <= 0 || N < 0 || M <= 0) return DCUE_ERR_INVALID;
+  Ws w;
+  carve(dims, B, N, M, nullptr, &w);
+  offsets_host[0] = (size_t)w.xfc;
+  offsets_host[1] = (size_t)w.dtp;
+  offsets_host[2] = (size_t)w.tidx;
   return DCUE_OK;
 }
 

@@ -488,6 +488,29 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
 // floats) and their chunk-ordered sums into dW [C][E][3], db [C]; dt [M][C] = dL/ds (read where
 // tidx != 255)
 int text_wgrad_nchunk(int M);
+// What launch_text_fwd launches for M items (host only; the launcher and dcue_debug_text_shape both
+// call it). The knobs are arguments: `chunked` DCUE_TEXT_FWD=chunked, `shape` 10 * waves + column
+// tiles per wave (81), `parts` DCUE_TEXT_PARTS (1; 2 needs the merge buffers: `merge`), `bpd`
+// DCUE_TEXT_BPD (6).
+struct TextFwdShape {
+  bool valid;      // false: no instantiation for the (waves, column tiles) asked for
+  bool full;       // k_text_fwd_full (else k_text_fwd)
+  int tb;          // 16-position tiles per workgroup: TBW (full) / TB (chunked)
+  int wv;          // full: waves; chunked: IPW, items per workgroup
+  int nct, bpd, nch, spl;  // full: column tiles per wave, B steps in flight, compile-time chunks (0: run time), parts
+  int nxcd;        // full: XCDs the units run on
+  long nunit;      // full: (item, part, column block) units; chunked: workgroups
+  unsigned grid;   // blocks launched (full: nxcd * ceil(units / nxcd) run, the rest exit at once)
+  unsigned gy;     // chunked: grid.y (column blocks)
+  size_t lds, lds_static;  // dynamic / static LDS bytes
+  int last;        // items of the last workgroup along M
+};
+TextFwdShape text_fwd_shape(int M, int T, int EP, int C, bool chunked, int shape, int parts, bool merge, int bpd);
+struct TextWgradShape {
+  int nchunk, items_per_chunk, last;  // last: items of the last chunk
+  bool reduce;                        // k_text_wreduce runs
+};
+TextWgradShape text_wgrad_shape(int M);
 int launch_text_wgrad(const TextBranch& tb, const int32_t* item_track, int M, const float* dt, const uint8_t* tidx,
                       float* wpart, float* dW, float* db, hipStream_t s);
 // SGD / Ranger over the dense buffer and the user table (optim.hip)

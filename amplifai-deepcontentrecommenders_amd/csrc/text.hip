@@ -603,11 +603,60 @@ __global__ __launch_bounds__(256) void k_text_wreduce(const float* __restrict__ 
 }
 
 template <int TB, int IPW>
-static int launch_text_fwd_t(const TextFwdArgs& a, hipStream_t s) {
-  dim3 grid((unsigned)((a.M + IPW - 1) / IPW), (unsigned)(a.C / 64));
-  DCUE_LAUNCH((k_text_fwd<TB, IPW>), grid, dim3(256), 0, s, a);
+static int launch_text_fwd_t(const TextFwdArgs& a, const TextFwdShape& sh, hipStream_t s) {
+  DCUE_LAUNCH((k_text_fwd<TB, IPW>), dim3(sh.grid / sh.gy, sh.gy), dim3(256), 0, s, a);
   DCUE_LAUNCH_CHECK();
   return DCUE_OK;
+}
+
+// Static LDS of k_text_fwd<TB, IPW>: xs[2][NROW][kTextRowH] halves + tok[NROW]
+static size_t text_chunked_lds(int tbt, int ipw) {
+  const size_t nrow = (size_t)ipw * (16 * tbt + 2);
+  return 2 * nrow * kTextRowH * sizeof(_Float16) + nrow * sizeof(int32_t);
+}
+
+TextFwdShape text_fwd_shape(int M, int T, int EP, int C, bool chunked, int shape, int parts, bool merge, int bpd) {
+  TextFwdShape sh = {};
+  sh.valid = true;
+  const int tb_ = T <= 16 ? 1 : T <= 32 ? 2 : T <= 64 ? 4 : 8;
+  // position parts (DCUE_TEXT_PARTS=2): two workgroups per (item, column block), given the merge buffers
+  const int spl = parts == 2 && tb_ >= 2 && merge ? 2 : 1;
+  const int tbw = tb_ / spl;  // 16-position tiles per workgroup
+  // the workgroup's staged rows must fit the LDS (config 4, two parts: 34 rows x 1,424 B = 48 KB)
+  const size_t lds = (size_t)(16 * tbw + 2) * text_full_pitch(EP) * sizeof(_Float16);
+  if (!chunked && lds <= 150 * 1024) {
+    int wv = shape / 10, nct = shape % 10;
+    if (wv < 1 || nct < 1 || C % (16 * wv * nct) || wv > 8) wv = C % 128 == 0 ? 8 : 4, nct = 1;
+    sh.full = true;
+    sh.tb = tbw; sh.wv = wv; sh.nct = nct; sh.spl = spl;
+    // work units on 4 XCDs while they fill at most 4 x 32 CUs at one workgroup per CU (the weight
+    // operand's per-XCD L2 fills halve); more units spread over all eight
+    sh.nunit = (long)M * (C / (16 * wv * nct)) * spl;
+    sh.nxcd = sh.nunit > 4 * 32 ? 8 : 4;
+    sh.grid = (unsigned)((sh.nunit + sh.nxcd - 1) / sh.nxcd * 8);
+    sh.gy = 1;
+    sh.lds = lds;
+    sh.lds_static = (size_t)(16 * tbw + 2) * 2 * sizeof(int32_t) + sizeof(unsigned);  // tok, tneed, s_arrived
+    sh.last = 1;
+    // B steps in flight: a divisor of the 3 * nchunk steps (registers: 8 * NCT per step); the config-4
+    // word width (EP = 320: 10 chunks) at compile time
+    const bool b6 = nct == 1 && tbw <= 4 && (EP / kTextKC) % 2 == 0;
+    sh.bpd = b6 ? 6 : 3;
+    sh.nch = b6 && EP == 320 ? 10 : 0;
+    // (A/B: the config-4 kernel's deeper weight prefetch, its default shape only)
+    if (sh.nch == 10 && tbw == 4 && wv == 8 && nct == 1 && spl == 1 && (bpd == 10 || bpd == 15)) sh.bpd = bpd;
+    sh.valid = (wv == 4 || wv == 8) && (nct == 1 || nct == 2);
+    return sh;
+  }
+  sh.tb = tb_;
+  sh.wv = 8 / tb_;  // IPW
+  sh.nct = 1; sh.spl = 1;
+  sh.gy = (unsigned)(C / 64);
+  sh.nunit = (long)((M + sh.wv - 1) / sh.wv) * sh.gy;
+  sh.grid = (unsigned)sh.nunit;
+  sh.lds_static = text_chunked_lds(sh.tb, sh.wv);
+  sh.last = M - (M - 1) / sh.wv * sh.wv;
+  return sh;
 }
 
 int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, float* out, long ld, uint8_t* tidx,
@@ -620,7 +669,8 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
   a.M = M; a.T = tb.T; a.E = tb.E; a.EP = tb.EP; a.C = tb.C; a.Creal = tb.Creal; a.pad = tb.pad;
   a.out = out; a.ld = ld; a.tidx = tidx;
   a.ticket = tb.ticket; a.part = tb.part;
-  if (tb.C % 64 || tb.T < 1 || tb.T > 128 || tb.E % 4 || tb.EP % kTextKC || tb.EP < tb.E) return DCUE_ERR_INVALID;
+  a.nxcd = 0;
+  if (tb.C % 64 || tb.T < 1 || tb.T > 128 || tb.E % 4 || tb.EP % kTextKC || tb.EP < tb.E || M < 1) return DCUE_ERR_INVALID;
   static const bool chunked = [] {
     const char* e = getenv("DCUE_TEXT_FWD");
     return e && e[0] == 'c';
@@ -640,39 +690,27 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
     const char* e = getenv("DCUE_TEXT_BPD");
     return e ? atoi(e) : 6;
   }();
-  const int tb_ = tb.T <= 16 ? 1 : tb.T <= 32 ? 2 : tb.T <= 64 ? 4 : 8;
-  // position parts (DCUE_TEXT_PARTS=2): two workgroups per (item, column block), given the merge buffers
-  const int spl = parts_env == 2 && tb_ >= 2 && tb.ticket && tb.part ? 2 : 1;
-  const int tbw = tb_ / spl;  // 16-position tiles per workgroup
-  // the workgroup's staged rows must fit the LDS (config 4, two parts: 34 rows x 1,424 B = 48 KB)
-  const size_t lds = (size_t)(16 * tbw + 2) * text_full_pitch(tb.EP) * sizeof(_Float16);
-  if (!chunked && lds <= 150 * 1024) {
-    int wv = shape / 10, nct = shape % 10;
-    if (tb.C % (16 * wv * nct) || wv > 8) wv = tb.C % 128 == 0 ? 8 : 4, nct = 1;
-    // work units on 4 XCDs while they fill at most 4 x 32 CUs at one workgroup per CU (the weight
-    // operand's per-XCD L2 fills halve); more units spread over all eight
-    const long nunit = (long)M * (tb.C / (16 * wv * nct)) * spl;
-    a.nxcd = nunit > 4 * 32 ? 8 : 4;
-    const unsigned grid = (unsigned)((nunit + a.nxcd - 1) / a.nxcd * 8);
+  const TextFwdShape sh = text_fwd_shape(M, tb.T, tb.EP, tb.C, chunked, shape, parts_env, tb.ticket && tb.part, bpd_env);
+  if (!sh.valid) return DCUE_ERR_INVALID;
+  if (sh.full) {
+    a.nxcd = sh.nxcd;
     auto pick = [&](auto kern) -> int {
       static bool attr = false;  // (one per instantiation)
       if (!attr) {
         DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
         attr = true;
       }
-      DCUE_LAUNCH(kern, dim3(grid), dim3(64 * wv), lds, s, a);
+      DCUE_LAUNCH(kern, dim3(sh.grid), dim3(64 * sh.wv), sh.lds, s, a);
       DCUE_LAUNCH_CHECK();
       return DCUE_OK;
     };
-    // B steps in flight: a divisor of the 3 * nchunk steps (registers: 8 * NCT per step); the config-4
-    // word width (EP = 320: 10 chunks) at compile time
-    const bool b6 = nct == 1 && tbw <= 4 && (tb.EP / kTextKC) % 2 == 0;
+    // the instantiation text_fwd_shape selected: <TBW, waves, NCT, BPD, NCH, parts>
 #define DCUE_TEXT_PICK_S(TBW, W, N, P, S)                                             \
-  if (tbw == TBW && spl == S) {                                                       \
-    if (P == 6 && tb.EP == 320) {                                                     \
-      if constexpr (TBW == 4 && W == 8 && N == 1 && S == 1) {                         \
-        if (bpd_env == 10) return pick(k_text_fwd_full<TBW, W, N, 10, 10, S>);        \
-        if (bpd_env == 15) return pick(k_text_fwd_full<TBW, W, N, 15, 10, S>);        \
+  if (sh.tb == TBW && sh.spl == S) {                                                  \
+    if (sh.nch == 10) {                                                               \
+      if constexpr (P == 6 && TBW == 4 && W == 8 && N == 1 && S == 1) {               \
+        if (sh.bpd == 10) return pick(k_text_fwd_full<TBW, W, N, 10, 10, S>);         \
+        if (sh.bpd == 15) return pick(k_text_fwd_full<TBW, W, N, 15, 10, S>);         \
       }                                                                               \
       return pick(k_text_fwd_full<TBW, W, N, P, 10, S>);                              \
     }                                                                                 \
@@ -686,11 +724,11 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
   DCUE_TEXT_PICK_S(2, W, N, P, 1)        \
   DCUE_TEXT_PICK_S(4, W, N, P, 1)        \
   DCUE_TEXT_PICK_S(8, W, N, P, 1)
-#define DCUE_TEXT_PICK(W, N)              \
-  if (wv == W && nct == N) {              \
-    if constexpr (N == 1)                 \
-      if (b6) { DCUE_TEXT_PICK_B(W, N, 6) } \
-    DCUE_TEXT_PICK_B(W, N, 3)             \
+#define DCUE_TEXT_PICK(W, N)                        \
+  if (sh.wv == W && sh.nct == N) {                  \
+    if constexpr (N == 1)                           \
+      if (sh.bpd >= 6) { DCUE_TEXT_PICK_B(W, N, 6) } \
+    DCUE_TEXT_PICK_B(W, N, 3)                       \
   }
     DCUE_TEXT_PICK(4, 1)
     DCUE_TEXT_PICK(8, 1)
@@ -701,10 +739,10 @@ int launch_text_fwd(const TextBranch& tb, const int32_t* item_track, int M, floa
 #undef DCUE_TEXT_PICK_S
     return DCUE_ERR_INVALID;
   }
-  if (tb.T <= 16) return launch_text_fwd_t<1, 8>(a, s);
-  if (tb.T <= 32) return launch_text_fwd_t<2, 4>(a, s);
-  if (tb.T <= 64) return launch_text_fwd_t<4, 2>(a, s);
-  return launch_text_fwd_t<8, 1>(a, s);
+  if (sh.tb == 1) return launch_text_fwd_t<1, 8>(a, sh, s);
+  if (sh.tb == 2) return launch_text_fwd_t<2, 4>(a, sh, s);
+  if (sh.tb == 4) return launch_text_fwd_t<4, 2>(a, sh, s);
+  return launch_text_fwd_t<8, 1>(a, sh, s);
 }
 
 // item chunks of the text weight gradient: one up to 128 items (the in-batch shapes: no partials),
@@ -714,6 +752,15 @@ int text_wgrad_nchunk(int M) {
   return n < 1 ? 1 : (n > 16 ? 16 : n);
 }
 
+TextWgradShape text_wgrad_shape(int M) {
+  TextWgradShape sh;
+  sh.nchunk = text_wgrad_nchunk(M);
+  sh.items_per_chunk = (M + sh.nchunk - 1) / sh.nchunk;
+  sh.last = M - (sh.nchunk - 1) * sh.items_per_chunk;
+  sh.reduce = sh.nchunk > 1;
+  return sh;
+}
+
 int launch_text_wgrad(const TextBranch& tb, const int32_t* item_track, int M, const float* dt, const uint8_t* tidx,
                       float* wpart, float* dW, float* db, hipStream_t s) {
   if (tb.C % kTwO || tb.T < 1 || tb.T > 128 || M < 1) return DCUE_ERR_INVALID;
@@ -721,8 +768,9 @@ int launch_text_wgrad(const TextBranch& tb, const int32_t* item_track, int M, co
   a.tokens = tb.tokens; a.item_track = item_track; a.words = tb.words;
   a.dt = dt; a.tidx = tidx;
   a.M = M; a.T = tb.T; a.E = tb.E; a.C = tb.C;
-  const int nchunk = text_wgrad_nchunk(M);
-  a.items_per_chunk = (M + nchunk - 1) / nchunk;
+  const TextWgradShape sh = text_wgrad_shape(M);
+  const int nchunk = sh.nchunk;
+  a.items_per_chunk = sh.items_per_chunk;
   a.dW = dW; a.db = db; a.wpart = wpart;
   const dim3 grid((unsigned)(tb.C / kTwO), (unsigned)((tb.E + kTwW - 1) / kTwW), (unsigned)nchunk);
   TimerScope tsc;  // (live timing: DCUE_TIMED_TEXT_WGRAD)
@@ -730,7 +778,7 @@ int launch_text_wgrad(const TextBranch& tb, const int32_t* item_track, int M, co
   DCUE_LAUNCH(k_text_wgrad, grid, dim3(256), 0, s, a);
   DCUE_LAUNCH_CHECK();
   TRY(timer_end(&tsc));
-  if (nchunk == 1) return DCUE_OK;
+  if (!sh.reduce) return DCUE_OK;
   const long n = (long)tb.C * tb.E * 3;
   DCUE_LAUNCH(k_text_wreduce, dim3((unsigned)((n + tb.C + 255) / 256)), dim3(256), 0, s, wpart, nchunk, n, tb.C,
               dW, db);

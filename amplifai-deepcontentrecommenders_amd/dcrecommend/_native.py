@@ -186,6 +186,9 @@ _SIGS = {
                                 ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_workspace_activations": ([ctypes.POINTER(Dims), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_workspace_text": ([ctypes.POINTER(Dims), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                             ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_debug_text_shape": ([ctypes.POINTER(Dims), ctypes.c_int32, _P, ctypes.c_int32], ctypes.c_int),
     "dcue_pack_weights": ([ctypes.POINTER(Model), _P], ctypes.c_int),
     "dcue_forward": ([ctypes.POINTER(Model), ctypes.POINTER(Batch), ctypes.POINTER(Tracks), _P,
                       ctypes.c_size_t, ctypes.c_int32, ctypes.c_float, _P, _P, _P, _P, _P], ctypes.c_int),
@@ -498,6 +501,35 @@ def launch_shape(dims, layout, B, N, M):
     return {"fwd": {l: tuple(w[5 * (l - 1):5 * l]) for l in range(1, 6)},
             "dgrad": {l: tuple(w[25 + 5 * (l - 2):25 + 5 * (l - 1)]) for l in range(2, 6)},
             "wgrad": wg, "tail": tuple(w[69:74])}
+
+
+TEXT_SHAPE_WORDS = 16  # DCUE_TEXT_SHAPE_WORDS
+_TEXT_FWD_FIELDS = ("kernel", "tb", "waves", "nct", "bpd", "nch", "nxcd", "units", "grid", "lds", "lds_static", "last")
+_TEXT_WGRAD_FIELDS = ("nchunk", "items_per_chunk", "last", "reduce")
+
+
+def text_shape(dims, M):
+    """The text branch's launches over M items (dcue_debug_text_shape; host only, no GPU needed):
+    {"fwd": {kernel "full" / "chunked", tb (TBW / TB), waves (chunked: items per workgroup), nct, bpd,
+    nch, nxcd, units, grid, lds, lds_static, last (items of the last workgroup)}, "wgrad": {nchunk,
+    items_per_chunk, last (items of the last chunk), reduce}}."""
+    buf = (ctypes.c_int32 * TEXT_SHAPE_WORDS)()
+    check(lib().dcue_debug_text_shape(ctypes.byref(dims), M, ctypes.cast(buf, _P), TEXT_SHAPE_WORDS),
+          "dcue_debug_text_shape")
+    w = list(buf)
+    fwd = dict(zip(_TEXT_FWD_FIELDS, w[:12]))
+    fwd["kernel"] = "chunked" if fwd["kernel"] else "full"
+    wg = dict(zip(_TEXT_WGRAD_FIELDS, w[12:16]))
+    wg["reduce"] = bool(wg["reduce"])
+    return {"fwd": fwd, "wgrad": wg}
+
+
+def workspace_text(dims, B, N, M):
+    """Byte offsets of the text branch's (xfc [M][text_dim + d_s] float, dtp [M][C_s] float, tidx
+    [M][C_s] uint8) inside a (B, N, M) workspace; an error outside the text tower."""
+    off = (ctypes.c_size_t * 3)()
+    check(lib().dcue_workspace_text(ctypes.byref(dims), B, N, M, off), "dcue_workspace_text")
+    return list(off)
 
 
 def debug_delay(site, microseconds):

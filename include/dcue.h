@@ -210,6 +210,14 @@ int dcue_workspace_outputs(const dcue_dims* dims, int32_t B, int32_t N, int32_t 
  * conv layers l = 1..5 (Lp = 33, 8, 2, 1, 1; C = H_s, H_s, H_s, H_s, d_s: storage widths). */
 int dcue_workspace_activations(const dcue_dims* dims, int32_t B, int32_t N, int32_t M,
                                size_t* offsets_host);
+/* Inspection (tests; added under ABI 17): byte offsets of the text branch's slices in the same
+ * workspace after a train step. [0] xfc, float [M][text_dim + d_s]: the fc input, the text features
+ * s in columns [0, text_dim), then bn5(y5); [1] dtp, float [M][C_s]: dL/ds, the text features'
+ * gradient before the ReLU / max routing; [2] tidx, uint8 [M][C_s]: the position of the maximum over
+ * the non-PAD positions (first maximum), 255 = no gradient (maximum <= 0, no valid position, or a
+ * storage channel >= text_dim). C_s = text_dim rounded up to 64, 128 or 256. DCUE_ERR_INVALID
+ * outside the text tower. */
+int dcue_workspace_text(const dcue_dims* dims, int32_t B, int32_t N, int32_t M, size_t* offsets_host);
 
 /* ------------------------------------------------------------------------- hot-path entries */
 /* Refresh wpack from params (after any host-side write of conv weights and after every Adam step). */
@@ -465,6 +473,21 @@ int dcue_debug_raise_fail_flags(uint32_t bits);
 #define DCUE_LAUNCH_SHAPE_WORDS 74
 int dcue_debug_launch_shape(const dcue_dims* dims, int32_t layout, int32_t B, int32_t N, int32_t M,
                             int32_t* out_host, int32_t cap);
+/* The text branch's launches over M items (text tower only; added under ABI 17; host only), from the
+ * functions launch_text_fwd / launch_text_wgrad call, with the A/B knobs unset. out_host gets
+ * DCUE_TEXT_SHAPE_WORDS int32 words (cap: its size):
+ *   [0]  forward kernel: 0 k_text_fwd_full (an item's sentence staged once), 1 k_text_fwd (chunked:
+ *        where the staged sentence would not fit 150 KB of LDS)
+ *   [1]  16-position tiles per workgroup (TBW / TB)     [2]  full: waves; chunked: items per workgroup
+ *   [3]  column tiles per wave (NCT)                    [4]  full: B steps in flight (BPD); chunked: 0
+ *   [5]  compile-time K chunks (NCH; 0: run time)       [6]  full: XCDs the units run on; chunked: 0
+ *   [7]  full: (item, column block) units; chunked: workgroups
+ *   [8]  blocks launched                                [9]  dynamic LDS bytes
+ *   [10] static LDS bytes                               [11] items of the last workgroup along M
+ *   [12] weight-gradient chunks                         [13] items per chunk
+ *   [14] items of the last chunk                        [15] 1: k_text_wreduce runs */
+#define DCUE_TEXT_SHAPE_WORDS 16
+int dcue_debug_text_shape(const dcue_dims* dims, int32_t M, int32_t* out_host, int32_t cap);
 
 /* ------------------------------------------------- data-parallel gradient exchange (RCCL) */
 /* One process per GPU; users are sharded over the ranks, so the only exchange of a step is the

@@ -171,3 +171,45 @@ def test_catalogue_draws(golden):
     assert np.array_equal(got, g["stream"])
     items = [indices[indptr[u]:indptr[u + 1]] for u in users]
     assert np.array_equal(O.catalogue_negatives(np.random.RandomState(77), g["split_items"], items, N), g["stream"])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_text_route_of_the_oracle_is_the_unrouted_form(dtype):
+    """text_oracle with a text_route: routed on the oracle's own first-maximum / ReLU decisions it is
+    the unrouted form bit for bit, values and gradients -- rows with PAD at the right, inside, at the
+    left and everywhere, a full-length row, and a small vocabulary so that maxima tie exactly."""
+    from oracle import text_oracle as TO
+    B, N, T, V, PAD = 3, 2, 9, 8, 0
+    torch.manual_seed(3)
+    p, b = TO.init_params(32, 32, 300, 5, 40, 12, V)
+    with torch.no_grad():
+        p["text.conv.weight"][::2, :, 0] = 0   # taps 0 and 2 off: z depends on the word alone, so a
+        p["text.conv.weight"][::2, :, 2] = 0   # repeated word ties exactly
+    p = {k: v.to(dtype) for k, v in p.items()}
+    b = {k: (v.to(dtype) if v.is_floating_point() else v.clone()) for k, v in b.items()}
+    gen = torch.Generator().manual_seed(4)
+    tok = torch.randint(1, V, (B * (1 + N), T), generator=gen, dtype=torch.int32)
+    tok[1, 5:] = PAD
+    tok[2, 3] = PAD
+    tok[3, :4] = PAD
+    tok[4] = PAD
+    u = torch.randint(0, 5, (B,), generator=gen)
+    pos = torch.randn(B, 128, 131, generator=gen).to(dtype)
+    neg = torch.randn(B, N, 128, 131, generator=gen).to(dtype)
+    r = TO.text_route(p, tok, PAD)
+    assert bool((r[4] == 255).all()) and bool((r != 255).any())
+    z = TO.text_preact(p, tok)
+    assert z.shape == (B * (1 + N), 40, T)
+    live = (tok != PAD).unsqueeze(1)
+    top = z.masked_fill(~live, float("-inf")).max(dim=2, keepdim=True).values
+    assert int(((z == top) & live).sum(dim=2).max()) > 1, "no exact tie: the first-maximum rule is not exercised"
+    assert torch.equal(TO.text_features(p, tok, PAD, r), TO.text_features(p, tok, PAD))
+    pt, nt = tok[:B], tok[B:].reshape(B, N, T)
+    l0, g0, out0 = TO.loss_and_grads(p, {k: v.clone() for k, v in b.items()}, u, pos, neg, pt, nt, PAD)
+    l1, g1, out1 = TO.loss_and_grads(p, {k: v.clone() for k, v in b.items()}, u, pos, neg, pt, nt, PAD, text_route=r)
+    assert float(l0) > 0 and torch.equal(l0, l1)
+    for a, c in zip(out0, out1):
+        assert torch.equal(a, c)
+    assert float(g0["text.conv.weight"].abs().max()) > 0
+    for k in g0:
+        assert torch.equal(g0[k], g1[k]), k
