@@ -137,6 +137,11 @@ class CropConfig(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("draw", ctypes.c_uint64)]
 
 
+class WeightTables(ctypes.Structure):
+    """dcue_weight_tables (dcue_sample_catalogue_weighted, added under ABI 17): device uint32 arrays."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("cum", "user_key", "user_skip", "user_weight")]
+
+
 CROP_FIRST, CROP_CENTER, CROP_GRID, CROP_RANDOM = 0, 1, 2, 3  # DCUE_CROP_*
 CROP_FLAG_BAD_EXTENT, CROP_FLAG_BAD_ROW = 1, 2
 CROP_FACTOR_DRAW0 = 1 << 32  # the item-factor passes' draws: 2^32 + j, apart from every epoch's
@@ -212,6 +217,9 @@ _SIGS = {
     "dcue_sample_inbatch": ([_P, ctypes.c_int32, ctypes.c_int32, _P, _P], ctypes.c_int),
     "dcue_sample_catalogue": ([_P, ctypes.c_int32, ctypes.c_uint32, _P, ctypes.c_int64, _P, _P, _P,
                                ctypes.c_int32, ctypes.c_int32, _P, _P], ctypes.c_int),
+    "dcue_sample_catalogue_weighted": ([_P, ctypes.c_int32, ctypes.c_uint32, _P, ctypes.c_int64, _P, _P,
+                                        ctypes.POINTER(WeightTables), _P, ctypes.c_int32, ctypes.c_int32, _P, _P],
+                                       ctypes.c_int),
     "dcue_build_catalogue_batch": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P], ctypes.c_int),
     "dcue_emb_log_bytes": ([ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_emb_log_init": ([ctypes.POINTER(Model), ctypes.c_int32, ctypes.c_int32, _P], ctypes.c_int),

@@ -17,15 +17,32 @@ import torch.nn.functional as F
 from scipy.sparse import csr_matrix
 from torch.utils.data import Dataset
 
+from dcrecommend.datasets.csr import MAX_TOTAL_WEIGHT, popularity_weights
+
 N_FRAMES = 131
 
 
 class DCUEDataset(Dataset):
 
     def __init__(self, triplets, metadata, neg_samples=20, split='train', n_users=20000, n_items=10000,
-                 song_artist_map=None, artist_bios=None, random_seed=None):
+                 song_artist_map=None, artist_bios=None, random_seed=None, neg_sampling='uniform', neg_alpha=0.75,
+                 neg_weights=None):
         """triplets: DataFrame (user_id, song_id, score) by column position; metadata: DataFrame with
-        song_id in column 1 and a `data_mel` path column (dcuedataset.py:17-31)."""
+        song_id in column 1 and a `data_mel` path column (dcuedataset.py:17-31).
+
+        neg_sampling (an MI355X addition): how a user's negatives are drawn from the split's songs the
+        user has not played. 'uniform': the reference's np.random.choice. 'popularity': in proportion
+        to (the song's number of users) ** neg_alpha, as integer weights (csr.popularity_weights).
+        'weights': in proportion to neg_weights, a non-negative integer array by item index (read at
+        the split's songs; 0: never a negative)."""
+        if neg_sampling not in ('uniform', 'popularity', 'weights'):
+            raise ValueError("neg_sampling must be 'uniform', 'popularity' or 'weights', got %r" % (neg_sampling,))
+        if (neg_sampling == 'weights') != (neg_weights is not None):
+            raise ValueError("neg_weights goes with neg_sampling='weights'")
+        self.neg_sampling = neg_sampling
+        self.neg_alpha = neg_alpha
+        self.neg_weights = neg_weights
+        self._neg_w = None
         self.triplets = triplets
         self.metadata = metadata
         self.neg_samples = neg_samples
@@ -118,6 +135,14 @@ class DCUEDataset(Dataset):
         """N catalogue negatives for one user, drawn on the host from the global numpy stream
         (dcuedataset.py:207-220); the trainer draws the same values on the GPU."""
         items = self.item_user.getcol(self.user_index[user_id]).nonzero()[0]
+        if self.neg_sampling != 'uniform':
+            # one bounded integer per negative over the candidates' cumulative integer weights
+            split = self.split_items()
+            cand = np.nonzero(~np.isin(split, items))[0]
+            cw = np.cumsum(self.negative_weights()[cand].astype(np.int64))
+            r = np.random.randint(0, cw[-1] if len(cw) else 0, self.neg_samples)
+            nonitems = split[cand[np.searchsorted(cw, r, side='right')]]
+            return [self.itemindex2songid[i] for i in nonitems]
         nonitems = self.all_items[(~np.in1d(self.all_items, items)) &
                                   np.in1d(self.all_items, self.uniq_song_idxs)]
         nonitems = np.random.choice(nonitems, self.neg_samples)
@@ -149,6 +174,29 @@ class DCUEDataset(Dataset):
     def split_items(self):
         """Sorted item indices of this split's songs (the `uniq_song_idxs` filter of :217)."""
         return np.sort(np.asarray(self.uniq_song_idxs, dtype=np.int64))
+
+    def negative_weights(self):
+        """uint32 weight of every position of split_items() under neg_sampling (ones for 'uniform');
+        their sum is at most 2^32 - 1."""
+        if self._neg_w is None:
+            split = self.split_items()
+            if self.neg_sampling == 'popularity':
+                counts = self.item_user.tocsr().getnnz(axis=1)[split]
+                w = popularity_weights(counts, self.neg_alpha)
+            elif self.neg_sampling == 'weights':
+                w = np.asarray(self.neg_weights)
+                if w.ndim != 1 or len(w) != self.n_items or not np.issubdtype(w.dtype, np.integer):
+                    raise ValueError("neg_weights must be an integer array with one weight per item index")
+                w = w[split]
+                if len(w) and int(w.min()) < 0:
+                    raise ValueError("negative weight")
+                if sum(int(x) for x in w) > MAX_TOTAL_WEIGHT:
+                    raise ValueError("the split's weights sum past 2^32 - 1")
+                w = w.astype(np.uint32)
+            else:
+                w = np.ones(len(split), dtype=np.uint32)
+            self._neg_w = w
+        return self._neg_w
 
     def split_users(self):
         return np.sort(np.asarray(self.uniq_user_idxs, dtype=np.int64))

@@ -28,7 +28,8 @@ import torch
 from torch.utils.data import RandomSampler
 
 from dcrecommend import _native as nat
-from dcrecommend.datasets.csr import check_catalogue_users, saturated_users, user_split_ranks
+from dcrecommend.datasets.csr import (check_catalogue_users, saturated_users, user_split_ranks,
+                                      weighted_saturated_users, weighted_split_tables)
 from dcrecommend.dcue.dcue import DCUENet
 from dcrecommend.dcue.plan import TrainPlan
 from dcrecommend.nn import rank
@@ -73,7 +74,8 @@ class _IndexBatches:
 
 class _Negatives:
     """GPU catalogue sampler over one split (datasets/dcuedataset.py:207-220): the user -> split-rank
-    CSR, the split's item list and the MT19937 stream on the device."""
+    CSR, the split's item list and the MT19937 stream on the device. A dataset whose neg_sampling is
+    not 'uniform' draws in proportion to its negative_weights() (dcue_sample_catalogue_weighted)."""
 
     def __init__(self, ds, device):
         self.ds = ds
@@ -87,6 +89,13 @@ class _Negatives:
         self.reseed = ds.random_seed is not None
         self.seed = int(ds.random_seed) if self.reseed else 0
         self.saturated = saturated_users(indptr, len(split))  # usually empty
+        self.tables = None
+        if getattr(ds, "neg_sampling", "uniform") != "uniform":
+            host = weighted_split_tables(indptr, ranks, ds.negative_weights())
+            self.saturated = weighted_saturated_users(host[3])
+            # the struct holds addresses: the tensors stay referenced beside it
+            self._tables = [torch.from_numpy(a if len(a) else np.zeros(1, np.uint32)).to(device) for a in host]
+            self.tables = nat.WeightTables(*[t.data_ptr() for t in self._tables])
 
     def check(self, users):
         """ValueError (numpy's) before a batch whose user has no candidate negative is sampled."""
@@ -94,6 +103,13 @@ class _Negatives:
             check_catalogue_users(users.cpu().numpy() if torch.is_tensor(users) else users, self.saturated)
 
     def draw(self, mt, users, N, out, stream=None):
+        if self.tables is not None:
+            nat.check(nat.lib().dcue_sample_catalogue_weighted(
+                None if self.reseed else nat.ptr(mt), int(self.reseed), self.seed, nat.ptr(self.split),
+                self.split.numel(), nat.ptr(self.indptr), nat.ptr(self.ranks), ctypes.byref(self.tables),
+                nat.ptr(users), users.numel(), N, nat.ptr(out),
+                nat.stream_handle(self.device) if stream is None else stream), "dcue_sample_catalogue_weighted")
+            return
         nat.check(nat.lib().dcue_sample_catalogue(
             None if self.reseed else nat.ptr(mt), int(self.reseed), self.seed, nat.ptr(self.split),
             self.split.numel(), nat.ptr(self.indptr), nat.ptr(self.ranks), nat.ptr(users), users.numel(), N,

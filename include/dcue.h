@@ -351,6 +351,35 @@ int dcue_sample_catalogue(dcue_mt_state* state, int32_t reseed, uint32_t seed,
                           const int32_t* user_split_rank, const int64_t* users, int32_t n_samples,
                           int32_t N, int64_t* out, void* stream);
 
+/* (added under ABI 17) Catalogue negatives drawn in proportion to integer weights. w[p] (uint32,
+ * zeros allowed) is the weight of split position p, W = sum(w) <= 2^32 - 1. For one sample of user u,
+ * with cand the split positions that are not the user's, ascending:
+ *   cw = cumsum(w[cand]);  W_u = cw[-1];  r = np.random.randint(0, W_u, N)   (legacy RandomState)
+ *   out = split_items[cand[searchsorted(cw, r, side='right')]]
+ * bit for bit: every draw is one bounded integer of the masked-rejection stream dcue_sample_catalogue
+ * consumes, and the map from a draw to an item is integer arithmetic. A zero-weight song is never
+ * drawn. W_u == 0 (numpy raises ValueError): the row is -1 and consumes no draw; callers check on the
+ * host first. W_u == 1 consumes no draw either. w == 1 everywhere reproduces dcue_sample_catalogue:
+ * the same outputs and the same state afterwards.
+ * The tables are device arrays built once per dataset from (user_indptr, user_split_rank, w), with
+ * rank_e the user's e-th split rank (datasets/csr.py weighted_split_tables builds them):
+ *   cum[n_split + 1]     cum[p] = w[0] + ... + w[p-1]                       (cum[n_split] = W)
+ *   user_skip[nnz]       by CSR entry: E_e = w[rank_0] + ... + w[rank_{e-1}] within the user's list
+ *   user_key[nnz]        by CSR entry: K_e = cum[rank_e] - E_e, non-decreasing within a list
+ *   user_weight[n_users] W_u = W - (the sum of w over the user's list)
+ * Both protocols of dcue_sample_catalogue and its other arguments; N <= 1024. */
+typedef struct dcue_weight_tables {
+  const uint32_t* cum;
+  const uint32_t* user_key;
+  const uint32_t* user_skip;
+  const uint32_t* user_weight;
+} dcue_weight_tables;
+int dcue_sample_catalogue_weighted(dcue_mt_state* state, int32_t reseed, uint32_t seed,
+                                   const int64_t* split_items, int64_t n_split,
+                                   const int64_t* user_indptr, const int32_t* user_split_rank,
+                                   const dcue_weight_tables* tables, const int64_t* users,
+                                   int32_t n_samples, int32_t N, int64_t* out, void* stream);
+
 /* -------------------------------------------------------------------------- step plans */
 /* A training-step plan: the step's kernels (optionally the in-batch negative draw, then the train
  * forward and backward of dcue_forward/dcue_train_backward) bound once and issued by one host call

@@ -85,7 +85,14 @@ def parse(argv=None):
     ap.add_argument("--crop-seed", type=int, default=0, help="DCUE(crop_seed=...): the seed of --crop epoch's windows")
     ap.add_argument("--factor-crops", choices=["random", "grid"], default="random",
                     help="DCUE(factor_crops=...), with --crop epoch: the windows the item factors average over")
+    ap.add_argument("--neg-sampling", choices=["uniform", "popularity"], default="uniform",
+                    help="DCUEDataset(neg_sampling=...) of the TRAIN set: 'popularity' draws a user's negatives in "
+                         "proportion to (a song's number of users) ** --neg-alpha instead of uniformly. The val and "
+                         "test sets keep uniform negatives, so their losses stay comparable across runs")
+    ap.add_argument("--neg-alpha", type=float, default=0.75, help="the exponent of --neg-sampling popularity")
     args = ap.parse_args(argv)
+    if args.neg_alpha < 0:
+        ap.error("--neg-alpha must be >= 0, got %r" % args.neg_alpha)
     if bool(args.eval_k) != bool(args.eval_out):
         ap.error("--eval-k and --eval-out go together")
     if args.eval_k:
@@ -152,7 +159,8 @@ def main(argv=None):
         meta = pd.read_csv(args.metadata)
         triplets_path, metadata_path = args.triplets, args.metadata
 
-    train = DCUEDataset(trip.copy(), meta, neg_samples=args.neg_batch_size, split="train")
+    train = DCUEDataset(trip.copy(), meta, neg_samples=args.neg_batch_size, split="train",
+                        neg_sampling=args.neg_sampling, neg_alpha=args.neg_alpha)
     val = DCUEDataset(trip.copy(), meta, neg_samples=args.neg_batch_size, split="val")
     test = DCUEDataset(trip.copy(), meta, neg_samples=args.neg_batch_size, split="test")
     pred = DCUEPredset(trip.copy(), meta, split="val")
