@@ -154,6 +154,9 @@ RESAMPLE_QUALITIES = {"best": (64, 14.769656459379492, 0.9475937167399596), "fas
 RESAMPLE_MAX_TABLE_BYTES = 16 << 20  # DCUE_RESAMPLE_MAX_TABLE_BYTES
 FOLDIN_MAX_STEPS, FOLDIN_MAX_NEG, FOLDIN_MAX_POS = 4096, 256, 1024
 FOLDIN_EMPTY, FOLDIN_NONFINITE, FOLDIN_DROPPED = 1, 2, 4  # out_flags bits
+# dcue_select_negatives (hard negatives, added under ABI 17): DCUE_SELECT_MAX_POOL, DCUE_SELECT_FLAG_*
+SELECT_MAX_POOL = 1024
+SELECT_FLAG_NONFINITE, SELECT_FLAG_BAD_ID = 1, 2
 MT_STATE_BYTES = 624 * 4 + 16
 MAX_LOG_CAP = 256
 ABI_VERSION = 17
@@ -220,6 +223,8 @@ _SIGS = {
     "dcue_sample_catalogue_weighted": ([_P, ctypes.c_int32, ctypes.c_uint32, _P, ctypes.c_int64, _P, _P,
                                         ctypes.POINTER(WeightTables), _P, ctypes.c_int32, ctypes.c_int32, _P, _P],
                                        ctypes.c_int),
+    "dcue_select_negatives": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, ctypes.c_int32,
+                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "dcue_build_catalogue_batch": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P], ctypes.c_int),
     "dcue_emb_log_bytes": ([ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_emb_log_init": ([ctypes.POINTER(Model), ctypes.c_int32, ctypes.c_int32, _P], ctypes.c_int),
@@ -590,6 +595,38 @@ def crop_tracks(data, frame_ptr, cfg, out, rows=None, starts=None, flags=None, s
                                  0 if out.dtype == torch.float16 else 1, ptr(starts), ptr(flags),
                                  stream_handle(out.device) if stream is None else stream), "dcue_crop_tracks")
     return flags[:n_out]
+
+
+def select_negatives(user_feat, item_feat, users, pool, N, H, out=None, out_hard=None, out_flags=None, stream=None):
+    """dcue_select_negatives: out of pool [n, P] (int64 item indices) keep per row the H that the fp32
+    factors user_feat [n_users, d] / item_feat [n_items, d] score highest for users [n], filled up to N
+    with the pool's other draws in order. Returns (out [n, N] int64, out_hard [n] int32, out_flags [n]
+    int32), device tensors; the call does not wait for its stream."""
+    for name, x, dt in (("user_feat", user_feat, torch.float32), ("item_feat", item_feat, torch.float32),
+                        ("users", users, torch.int64), ("pool", pool, torch.int64)):
+        require_gpu(x, name)
+        if x.dtype != dt or not x.is_contiguous():
+            raise ValueError("select_negatives: %s must be a contiguous %s tensor" % (name, dt))
+    if user_feat.dim() != 2 or item_feat.dim() != 2 or user_feat.shape[1] != item_feat.shape[1]:
+        raise ValueError("select_negatives: user_feat and item_feat must be [rows, d] with one d")
+    n = users.numel()
+    if pool.dim() != 2 or pool.shape[0] != n:
+        raise ValueError("select_negatives: pool must be [len(users), P]")
+    dev = pool.device
+    out = torch.empty((n, max(int(N), 0)), dtype=torch.int64, device=dev) if out is None else out
+    out_hard = torch.empty(n, dtype=torch.int32, device=dev) if out_hard is None else out_hard
+    out_flags = torch.empty(n, dtype=torch.int32, device=dev) if out_flags is None else out_flags
+    for name, x, dt, numel in (("out", out, torch.int64, n * int(N)), ("out_hard", out_hard, torch.int32, n),
+                               ("out_flags", out_flags, torch.int32, n)):
+        if x.dtype != dt or not x.is_contiguous() or x.numel() != numel:
+            raise ValueError("select_negatives: %s must be a contiguous %s tensor of %d elements" % (name, dt, numel))
+    if n == 0:  # empty tensors have no address to pass
+        return out, out_hard, out_flags
+    check(lib().dcue_select_negatives(ptr(user_feat), user_feat.shape[0], ptr(item_feat), item_feat.shape[0],
+                                      user_feat.shape[1], ptr(users), ptr(pool), n, pool.shape[1], int(N), int(H),
+                                      ptr(out), ptr(out_hard), ptr(out_flags),
+                                      stream_handle(dev) if stream is None else stream), "dcue_select_negatives")
+    return out, out_hard, out_flags
 
 
 def crop_starts_host(cfg, lengths, track_ids=None):

@@ -22,6 +22,7 @@ the reference's trajectory: tests/golden/fit.npz.
 """
 import ctypes
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -137,7 +138,7 @@ class DCUE(Trainer):
                  margin=0.2, optimize='adam', lr=0.00001, beta_one=0.9, beta_two=0.99, eps=1e-8,
                  weight_decay=0, restart_period=30, t_mult=2, num_epochs=90, model_type='truedcuemel1dbn',
                  eval_pct=0.025, val_pct=1.0, device=None, defer_embedding=True, crop='load', crop_seed=0,
-                 factor_crops='random'):
+                 factor_crops='random', neg_pool=None, neg_hard=None):
         """Arguments as nn/dcue.py:47-50; device (default cuda:current) and defer_embedding (the
         bit-identical deferred user-table Adam, dcrecommend.optim.NativeAdam) are MI355X additions.
 
@@ -145,7 +146,14 @@ class DCUE(Trainer):
         keeps the full-length tracks in HBM (DCUEItemset.track_store) and re-cuts the whole table in
         place before every training sub-epoch, a random window per track from (crop_seed, nn_epoch)
         (include/dcue.h dcue_crop_tracks); the item factors then average n_iter real passes over
-        factor_crops windows: 'random' (the same draws every epoch) or 'grid' (evenly spread)."""
+        factor_crops windows: 'random' (the same draws every epoch) or 'grid' (evenly spread).
+
+        neg_pool=P (N <= P <= 1024, N the negatives per row) turns hard negatives on for the training
+        sub-epochs: every row draws P candidates where it drew N, and keeps the neg_hard (default N // 2;
+        0 <= neg_hard <= N) that the factors of the last sub-epoch score highest for its user, filled up
+        to N with the pool's leading other draws (include/dcue.h dcue_select_negatives). None, the
+        default, is the plain sampler. Validation and test losses always use N plain draws."""
+        self._check_neg_pool(neg_pool, neg_hard)
         if crop not in ('load', 'epoch'):
             raise ValueError("crop must be 'load' or 'epoch', got %r" % (crop,))
         if factor_crops not in ('random', 'grid'):
@@ -154,6 +162,9 @@ class DCUE(Trainer):
         self.crop = crop
         self.crop_seed = int(crop_seed)
         self.factor_crops = factor_crops
+        self.neg_pool = None if neg_pool is None else int(neg_pool)
+        self.neg_hard = None if neg_hard is None else int(neg_hard)
+        self._on_negatives = None  # tests: called as (step, users, pool, negs, hard) on the sampling stream
         self.feature_dim = feature_dim
         self.conv_hidden = conv_hidden
         self.batch_size = batch_size
@@ -274,6 +285,31 @@ class DCUE(Trainer):
         cfg = nat.crop_config(nat.CROP_RANDOM, seed=self.crop_seed, draw=self.nn_epoch if draw is None else draw)
         return nat.crop_tracks(data, frame_ptr, cfg, self._tracks)
 
+    @staticmethod
+    def _check_neg_pool(neg_pool, neg_hard, N=None):
+        """ValueError for a neg_pool / neg_hard pair no sub-epoch could run with; the bounds against N
+        once it is known. Returns (P, H), or None with the mode off."""
+        if neg_pool is None:
+            if neg_hard is not None:
+                raise ValueError("neg_hard needs neg_pool: without a pool there is nothing to select from")
+            return None
+        for name, v in (("neg_pool", neg_pool), ("neg_hard", neg_hard)):
+            if v is not None and (isinstance(v, bool) or int(v) != v):
+                raise ValueError("%s must be an integer, got %r" % (name, v))
+        P = int(neg_pool)
+        if not 1 <= P <= nat.SELECT_MAX_POOL:
+            raise ValueError("neg_pool must be in 1..%d, got %d" % (nat.SELECT_MAX_POOL, P))
+        if neg_hard is not None and not 0 <= int(neg_hard) <= P:
+            raise ValueError("neg_hard must be in 0..neg_pool, got %d" % int(neg_hard))
+        if N is None:
+            return P, neg_hard
+        if P < N:
+            raise ValueError("neg_pool must be at least the %d negatives per row, got %d" % (N, P))
+        H = N // 2 if neg_hard is None else int(neg_hard)
+        if H > N:
+            raise ValueError("neg_hard must be at most the %d negatives per row, got %d" % (N, H))
+        return P, H
+
     def _n_neg(self, ds):
         """Negatives per row: the dataset's neg_samples, as in the reference, where the trainer's
         neg_batch_size is never read (datasets/dcuedataset.py:18,219)."""
@@ -294,11 +330,27 @@ class DCUE(Trainer):
         step that consumes them (datasets/dcuedataset.py:207-256). Here the batches' negatives are
         drawn two steps ahead on a sampling stream -- in batch order on the one numpy-compatible
         MT19937 stream, so the very same negatives -- and each batch's item list is built there too,
-        so the plan also prepares the next batch's bn0 statistics beside the current step."""
-        self.model.train()
+        so the plan also prepares the next batch's bn0 statistics beside the current step.
+
+        With neg_pool=P each row draws P candidates there instead -- still the one stream, P draws per
+        row -- and dcue_select_negatives keeps the neg_hard that the factors score highest for the
+        row's user, on the sampling stream too, so the step schedule is the same. The factors are a
+        snapshot from the start of the sub-epoch: fit leaves them one sub-epoch old."""
         ds = loader.dataset if hasattr(loader, "dataset") else self.train_data
         neg = self._negatives(ds)
         B, N = self.batch_size, self._n_neg(ds)
+        select = self._check_neg_pool(self.neg_pool, self.neg_hard, N)
+        if select is not None:
+            if self.user_factors is None or self.item_factors is None:
+                # called outside fit: once, and torch's global stream (the batch order) stays put
+                item_data = self.item_data if self.item_data is not None else self._tracks_src
+                with torch.random.fork_rng(devices=[]):
+                    self._user_factors(item_data)
+                    self._item_factors(item_data)
+            P, H = select
+            user_feat = self.user_factors.contiguous()
+            item_feat = self._item_feat_by_index().contiguous()
+        self.model.train()
         plan = self._train_plan(N)
         if self._store is not None:
             # before the sampling stream joins the main one below: every later reader of the table --
@@ -317,7 +369,15 @@ class DCUE(Trainer):
         ready = [torch.cuda.Event() for _ in range(3)]
         done = [torch.cuda.Event() for _ in range(3)]
         loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
-        samp.wait_stream(main)  # the sampler state and the row tables are written on the main stream
+        if select is not None:
+            pool = [torch.empty((B, P), dtype=torch.int64, device=dev) for _ in range(3)]
+            hard = [torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3)]
+            # every batch's flags stay on the device to the end of the sub-epoch: nothing waits for them
+            flags = torch.zeros((max(len(batches), 1), B), dtype=torch.int32, device=dev)
+            select_fn = nat.lib().dcue_select_negatives
+            feat_args = (nat.ptr(user_feat), user_feat.shape[0], nat.ptr(item_feat), item_feat.shape[0],
+                         user_feat.shape[1])
+        samp.wait_stream(main)  # the sampler state, the row tables and the factors: written on the main stream
 
         def prepare(s):
             k = s % 3
@@ -326,7 +386,15 @@ class DCUE(Trainer):
                 torch.index_select(users_all, 0, r, out=users[k])
                 torch.index_select(items_all, 0, r, out=pos[k])
                 neg.check(users[k])
-                neg.draw(mt, users[k], N, negs[k], stream=samp.cuda_stream)
+                if select is None:
+                    neg.draw(mt, users[k], N, negs[k], stream=samp.cuda_stream)
+                else:
+                    neg.draw(mt, users[k], P, pool[k], stream=samp.cuda_stream)
+                    nat.check(select_fn(*feat_args, nat.ptr(users[k]), nat.ptr(pool[k]), B, P, N, H, nat.ptr(negs[k]),
+                                        nat.ptr(hard[k]), ctypes.c_void_p(flags.data_ptr() + 4 * B * s),
+                                        samp.cuda_stream), "dcue_select_negatives")
+                    if self._on_negatives is not None:
+                        self._on_negatives(s, users[k], pool[k], negs[k], hard[k])
                 nat.check(nat.lib().dcue_build_catalogue_batch(nat.ptr(pos[k]), nat.ptr(negs[k]), B, N,
                                                                nat.ptr(items[k]), samp.cuda_stream),
                           "dcue_build_catalogue_batch")
@@ -349,6 +417,16 @@ class DCUE(Trainer):
                 prepare(s + 2)
         main.wait_stream(samp)
         _mt_to_numpy(mt)
+        if select is not None:
+            # one device word, read once: nothing waited for the flags while the steps ran
+            word = int((flags & nat.SELECT_FLAG_NONFINITE).max() | (flags & nat.SELECT_FLAG_BAD_ID).max())
+            if word & nat.SELECT_FLAG_BAD_ID:
+                raise RuntimeError("hard negatives: a user or item index lies outside the factor tables "
+                                   "(%d users, %d items): the factors do not belong to this dataset"
+                                   % (user_feat.shape[0], item_feat.shape[0]))
+            if word & nat.SELECT_FLAG_NONFINITE:
+                warnings.warn("hard negatives: a factor score was NaN or infinite during this sub-epoch; "
+                              "a NaN score is never chosen as hard", RuntimeWarning)
         return n * B, float(loss_sum) / max(n * B, 1)
 
     def _eval_epoch(self, loader):
@@ -962,7 +1040,7 @@ class DCUE(Trainer):
                 "lr", "beta_one", "beta_two", "eps", "weight_decay", "restart_period", "t_mult", "num_epochs",
                 "model_type", "eval_pct", "val_pct", "n_users", "n_items", "epoch_size", "nn_epoch",
                 "best_val_map", "best_val_auc", "best_val_loss", "metadata_path", "triplets_path", "model_dir",
-                "defer_embedding", "crop", "crop_seed", "factor_crops")
+                "defer_embedding", "crop", "crop_seed", "factor_crops", "neg_pool", "neg_hard")
     _TENSORS = ("item_factors", "user_factors", "best_item_factors", "best_user_factors")
 
     def _checkpoint(self):

@@ -380,6 +380,40 @@ int dcue_sample_catalogue_weighted(dcue_mt_state* state, int32_t reseed, uint32_
                                    const dcue_weight_tables* tables, const int64_t* users,
                                    int32_t n_samples, int32_t N, int64_t* out, void* stream);
 
+/* (added under ABI 17) Hard negatives: out of a pool of P sampled candidates per row, keep the H that
+ * the given factors score highest for the row's user, and fill the row up to N with the pool's other
+ * draws in the order they were drawn (dynamic negative sampling).
+ *   user_feat [n_users][d], item_feat [n_items][d]: fp32, dense rows of exactly d floats, 1 <= d <= 256
+ *     (d need not be a multiple of 4: rows of d = 30 are only 8-byte aligned);
+ *   users [n_samples]; pool [n_samples][P]: item indices as dcue_sample_catalogue* writes them;
+ *   out [n_samples][N], out_hard [n_samples], out_flags [n_samples].
+ * Score of pool position p for row b: nn.CosineSimilarity's u.c / (max(|u|, 1e-8) * max(|c|, 1e-8)) in
+ * fp32, a function of the two rows' values only -- not of p, b, P, N, H, n_samples or how rows are
+ * batched. Splitting a call's rows over several calls therefore gives the same bits, and item rows
+ * that are bitwise equal tie exactly (-0 and +0 are one score).
+ * Hard set: a position is eligible when its id is in [0, n_items), it is the first occurrence of that
+ * id in the row, and its score is not NaN. The h = min(H, #eligible) best eligible positions by (score
+ * descending, position ascending) are hard; out[b][0:h] holds their ids in ascending pool position and
+ * out_hard[b] = h.
+ * Fill: out[b][h:N] holds the first N - h pool positions not chosen as hard, in pool order, ids copied
+ * as they are: duplicates and -1 pass through (dcue_build_catalogue_batch maps -1 to item 0). H = 0
+ * returns pool[b][0:N], and the fill is distributed as the base sampler's draws.
+ * out_flags[b]: DCUE_SELECT_FLAG_NONFINITE a score was NaN or infinite; DCUE_SELECT_FLAG_BAD_ID an id
+ * was outside [0, n_items) -- such an id is never hard and never addresses item_feat -- or the row's
+ * user id was outside [0, n_users), and the row then has h = 0.
+ * Required: 1 <= N <= P <= DCUE_SELECT_MAX_POOL, 0 <= H <= N, n_samples >= 0 (0 is a no-op success).
+ * Every argument is validated on the host before the first device call (DCUE_ERR_INVALID: a null
+ * pointer, a negative count, d < 1, N, P or H out of range; DCUE_ERR_UNSUPPORTED: d > 256). No
+ * workspace. The call does not synchronise `stream`: the trainer runs it on its sampling stream, two
+ * steps ahead of the step that consumes the row. */
+#define DCUE_SELECT_MAX_POOL 1024
+#define DCUE_SELECT_FLAG_NONFINITE 1
+#define DCUE_SELECT_FLAG_BAD_ID 2
+int dcue_select_negatives(const float* user_feat, int64_t n_users, const float* item_feat, int64_t n_items,
+                          int32_t d, const int64_t* users, const int64_t* pool, int32_t n_samples,
+                          int32_t P, int32_t N, int32_t H, int64_t* out, int32_t* out_hard,
+                          int32_t* out_flags, void* stream);
+
 /* -------------------------------------------------------------------------- step plans */
 /* A training-step plan: the step's kernels (optionally the in-batch negative draw, then the train
  * forward and backward of dcue_forward/dcue_train_backward) bound once and issued by one host call

@@ -90,9 +90,23 @@ def parse(argv=None):
                          "proportion to (a song's number of users) ** --neg-alpha instead of uniformly. The val and "
                          "test sets keep uniform negatives, so their losses stay comparable across runs")
     ap.add_argument("--neg-alpha", type=float, default=0.75, help="the exponent of --neg-sampling popularity")
+    ap.add_argument("--neg-pool", type=int, metavar="P",
+                    help="DCUE(neg_pool=...): hard negatives for the training sub-epochs. Every row draws P "
+                         "candidates (--neg-batch-size <= P <= 1024) and keeps the --neg-hard that the last "
+                         "sub-epoch's factors score highest for its user, filled up with the other draws in order "
+                         "(dcue_select_negatives). Default: the plain sampler. Val and test losses keep plain draws")
+    ap.add_argument("--neg-hard", type=int, metavar="H",
+                    help="DCUE(neg_hard=...), with --neg-pool: hard negatives per row, 0 <= H <= --neg-batch-size "
+                         "(default: half of --neg-batch-size)")
     args = ap.parse_args(argv)
     if args.neg_alpha < 0:
         ap.error("--neg-alpha must be >= 0, got %r" % args.neg_alpha)
+    if args.neg_hard is not None and args.neg_pool is None:
+        ap.error("--neg-hard needs --neg-pool")
+    if args.neg_pool is not None and not args.neg_batch_size <= args.neg_pool <= 1024:
+        ap.error("--neg-pool must be in --neg-batch-size..1024, got %r" % args.neg_pool)
+    if args.neg_hard is not None and not 0 <= args.neg_hard <= args.neg_batch_size:
+        ap.error("--neg-hard must be in 0..--neg-batch-size, got %r" % args.neg_hard)
     if bool(args.eval_k) != bool(args.eval_out):
         ap.error("--eval-k and --eval-out go together")
     if args.eval_k:
@@ -170,7 +184,8 @@ def main(argv=None):
                 neg_batch_size=args.neg_batch_size, u_embdim=args.u_embdim, margin=args.margin, lr=args.lr,
                 weight_decay=args.weight_decay, num_epochs=args.num_epochs, eval_pct=args.eval_pct,
                 val_pct=args.val_pct, optimize=args.optimize, model_type=args.model_type, crop=args.crop,
-                crop_seed=args.crop_seed, factor_crops=args.factor_crops)
+                crop_seed=args.crop_seed, factor_crops=args.factor_crops, neg_pool=args.neg_pool,
+                neg_hard=args.neg_hard)
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
     if args.recommend_k > 0 and args.recommend_out:
