@@ -21,6 +21,9 @@ bool on_side_worker();  // side.hip: this thread is the side-issue worker
     if (::dcue::host_profile_on() && !::dcue::on_side_worker()) ::dcue::host_profile_mark(label); \
   } while (0)
 
+// an A/B knob's value starts with `c` (read once: `static const bool on = env_is(getenv("DCUE_..."), '1')`)
+inline bool env_is(const char* v, char c) { return v && v[0] == c; }
+
 // propagate a non-zero dcue_status
 #define TRY(x)                 \
   do {                         \
@@ -567,7 +570,7 @@ std::vector<CapturedTimer> timer_take_captured();
 // the recording stream after every event-bound kernel of a step (profiles/r03: the critical
 // chain's gaps).
 unsigned sync_event_flags();
-// side streams (capi.hip): three per device, plus a ring of fork/join events
+// side streams (streams.hip): three per device, plus a ring of fork/join events
 struct SidePool {
   // st[0]: user tower + user-table Adam; st[1], st[2]: weight gradients of layers 5..2
   // (alternating). Three side streams + the caller's = the box's 4 hardware queues: a fifth stream
@@ -584,6 +587,7 @@ hipEvent_t ring_event(SidePool* p);
 
 // Set while a plan captures its step (bound launch events are not captured; records are).
 bool& capturing_step();
+int64_t launches_counted();  // count_launch's total (dcue_launch_count)
 
 // A fork point at the end of the launches made inside the scope, without an event-record packet:
 // the scope's ring event is bound to each launch (LaunchTag; the last binding is what a wait sees).
@@ -607,6 +611,25 @@ class ForkAfter {
 int wait_point(hipStream_t to, hipEvent_t ev);
 int join_user_stream(hipStream_t s);
 
+// One cross-stream order, a point on one stream that others wait for: a HIP event, a signal word with
+// the value it reaches (DevWait), or both where the producer makes both (the split plans' late Adam);
+// a consumer then takes the signal. Empty: nothing to wait for.
+struct Edge {
+  hipEvent_t ev = nullptr;
+  DevWait sig{};
+  bool dev() const { return sig.flag != nullptr; }
+};
+// Consumer side: stream `to` waits for e[0..n) -- the signal edges through one k_wait_signals relay (at
+// most kWaitSignalsMax), then the others' events through wait_point, in order.
+int wait_edges(hipStream_t to, const Edge* e, int n);
+// ... for a consumer whose first kernel polls at its own start: *poll receives the edge's signal for
+// that kernel's arguments (flag null: none); only an event edge is waited for on the stream.
+int wait_or_poll(hipStream_t to, const Edge& e, DevWait* poll);
+// Producer side: the next value of a plan's signal word `slot` (StepOpts::sig / sig_issued), `n` adds
+// past the last one issued. It advances the host's counter: called on the thread that issues the
+// step, before the closure that uses the value is posted.
+DevWait next_signal(unsigned* sig, unsigned* issued, int slot, unsigned n = 1);
+
 // Side-stream issue on a second host thread (side.hip). run(fn) posts fn to the device's worker
 // (FIFO) and returns its sequence number, or runs it here (returning 0, status in *inline_status)
 // when the worker is off (DCUE_SIDE_THREAD=0), under stream capture, or on the worker itself.
@@ -628,9 +651,7 @@ class SideQueue {
   uint64_t last_ = 0;
 };
 bool on_side_worker();
-// split plans: one wait before conv 1 for the previous step's late Adam, which covers the prepared
-// inputs (capi.hip)
-bool late_wait_at_conv1();
+bool late_wait_at_conv1();  // DCUE_LATE_WAIT=conv1 (step_backward.hip)
 
 // ------------------------------------------------------------- ranking / top-K (rank.hip, topk.hip)
 // factor rows are normalised into rows of DP = d rounded up to 16 floats (the MFMA k split)
@@ -672,19 +693,21 @@ void frz_forget(const dcue_emb_log* hdr);
 //  -- only to show tests/test_gpu_races.py failing on them
 bool legacy_orders();
 
-// ------------------------------------------------------------- step implementation (capi.hip)
+// ----------------------------------- step implementation (step_forward.hip, step_backward.hip)
 struct StepOpts {
-  hipEvent_t wait_inputs = nullptr;  // plans: the next step's prepared inputs; the caller's stream
-                                     // waits for it before the conv-1 weight gradient
-  uint64_t wait_inputs_seq = 0;      // ... once the side-issue thread has recorded it (SideQueue)
+  // plans: the next step's prepared inputs; the caller's stream waits for it before the conv-1 weight
+  // gradient (round 6: that kernel polls the signal), once the side-issue thread has issued it (SideQueue)
+  Edge inputs;
+  uint64_t wait_inputs_seq = 0;
   // plans: the next step's input preparation (lookahead), issued by the backward on the side path
   // once the dgrad chain's first fork point exists (its argument: that point, which orders it after
   // everything the caller enqueued before the step); the conv-1 weight gradient's wait for
-  // wait_inputs then waits for it to be issued
+  // `inputs` then waits for it to be issued
   const std::function<int(hipEvent_t)>* ahead = nullptr;
-  // plans: a point on the caller's stream at the launch's start (the user tower waits for it);
-  // null: the forward records one
-  hipEvent_t ev_in = nullptr;
+  // plans: a point on the caller's stream at the launch's start (the user tower and the text branch wait
+  // for it); empty: the forward records one. Round 7: a signal raised by the forward's first kernel on
+  // that stream (conv 1: the plan sets it only where conv 1 is that kernel); no event is then recorded
+  Edge start;
   dcue_comm* sync_bn = nullptr;  // SyncBN: BatchNorm sums all-reduced over this communicator's ranks
   bool prologue_done = false;  // counts written + accumulators cleared by the prologue
   bool fuse_score = false;     // train forward also runs the hinge backward (k_score_fused)
@@ -712,24 +735,15 @@ struct StepOpts {
   // bn1 (segments [0, DCUE_SEG_LATE)) right after its conv-1 tail, and the user stream the rest once
   // the side streams' gradients are in -- the caller's stream never waits for the join. *late_done
   // receives the user stream's point after that part; the next forward waits for it before conv 2
-  // (the first reader of a late segment on the caller's stream).
+  // (the first reader of a late segment on the caller's stream): its event and, with `sig`, its signal.
   const dcue_adam_args* dense_split = nullptr;
-  hipEvent_t* late_done = nullptr;
-  hipEvent_t wait_late = nullptr;  // forward: the previous split step's late_done
+  Edge* late_done = nullptr;
+  Edge late;  // forward: the previous split step's *late_done
   // plans (round 6): device-side waits (DevWait) in place of the caller stream's event waits -- the
   // plan's signal words [kSigSlots] and its host counters of the values issued into them (null:
-  // event waits); late_wait: the previous step's late Adam (conv 2 waits for it instead of wait_late),
-  // *late_sig receives this step's; inputs_wait: the next step's prepared inputs (the conv-1 weight
-  // gradient waits for it instead of wait_inputs)
+  // event waits)
   unsigned* sig = nullptr;
   unsigned* sig_issued = nullptr;
-  DevWait late_wait{};
-  DevWait* late_sig = nullptr;
-  DevWait inputs_wait{};
-  // round 7: the step's start, raised by the forward's first kernel on the caller's stream (conv 1:
-  // the plan sets it only where conv 1 is that kernel) -- the user tower and the text branch wait for
-  // it on the device instead of for ev_in, which is then null and not recorded
-  DevWait start_wait{};
   // the step's per-item copy lists (gather layout, built by the plan's prologue; StepPrologue)
   const int32_t* copy_ptr = nullptr;
   const int32_t* copy_idx = nullptr;

@@ -48,19 +48,18 @@ struct dcue_plan {
   const int32_t* next_items = nullptr;
   long launches = 0;
   hipEvent_t tails[2] = {};       // the last launched step's end (StepOpts::tails)
-  hipEvent_t late_done = nullptr; // the last split step's late-segment Adam (StepOpts::dense_split)
-  hipEvent_t inputs_ready = nullptr;  // the next step's inputs (prologue + lookahead) on wgrad stream 0
+  // the last split step's late-segment Adam (StepOpts::dense_split): its event and, with device-side
+  // waits, its signal -- what the next step's conv 2 waits for
+  dcue::Edge late_done;
   int pending_flush = -1;         // step whose rolling-flush slice the next launch issues
   hipStream_t last_stream = nullptr;  // the caller's stream of the last launch
   dcue_comm* comm = nullptr;      // data-parallel exchange between backward and Adam (plan_step)
   bool sync_bn = false;           // SyncBN over `comm` (dcue_plan_set_sync_bn)
   long late = 0, n_dense = 0;     // flat-gradient floats: end of bn0/conv1/bn1, total
   int comm_world = 1;
-  // device-side waits (StepOpts::sig, DevWait): the plan's signal words, the values issued into
-  // them, and the last split step's late-Adam signal (what the next step's conv 2 waits for)
+  // device-side waits (StepOpts::sig, DevWait): the plan's signal words and the values issued into them
   unsigned* sig = nullptr;
   unsigned sig_issued[dcue::kSigSlots] = {};
-  dcue::DevWait late_sig{};
 };
 
 // DCUE_XQ_WAIT=event: the plan's caller-stream waits as HIP event waits (rounds 1-5; A/B). Also off
@@ -84,14 +83,12 @@ namespace {
 // the rest of the backward.
 int issue_step(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t, void* ws, size_t ws_bytes,
                const dcue_plan_config* cfg, const int64_t* users_src, const int32_t* items_src,
-               hipStream_t s, const dcue_adam_args* emb_adam = nullptr, bool captured = false) {
+               hipStream_t s) {
   dcue::StepOpts o;
   o.prologue_done = true;
   o.fuse_score = true;
-  o.emb_adam = emb_adam;
   hipEvent_t score_done = nullptr;
   o.score_done = &score_done;
-  (void)captured;
   int st = dcue::step_prologue(m, b, ws, ws_bytes,
                                (cfg->flags & DCUE_PLAN_SAMPLE_INBATCH) ? cfg->mt : nullptr, users_src,
                                items_src, s);
@@ -146,13 +143,10 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   const bool ahead = prepared && items_src == p->ahead_items[cur];
   p->ahead_items[cur] = nullptr;
   // DCUE_PROLOGUE_FIRST=1: the prologue closure is posted before the forward (A/B)
-  static const bool prologue_first = [] {
-    const char* e = getenv("DCUE_PROLOGUE_FIRST");
-    return e && e[0] == '1';
-  }();
+  static const bool prologue_first = env_is(getenv("DCUE_PROLOGUE_FIRST"), '1');
   // device-side waits (no communicator: its exchange keeps the event orders)
   const bool dev = p->sig && !p->comm && dev_waits_on();
-  // A point on the caller's stream at this launch's start (ev_in): the user tower, this launch's
+  // A point on the caller's stream at this launch's start (`start`): the user tower, this launch's
   // prologue for the next step and the lookahead wait for it (it orders them after everything the
   // caller enqueued before the launch -- the batch indices, the announced next items -- and after the
   // last step, which ended on this stream).
@@ -163,55 +157,52 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   // word inside their kernels, the text branch behind a relay; no event is recorded. The first
   // launch, steps that start with another kernel (no lookahead: k_input_stats) and the prologue-first
   // order keep the event. So do steps whose conv 1 needs every CU (catalogue plans): the kernels that
-  // poll are resident before conv 1 starts -- k_user_fwd's workgroups and the 1024-thread prologue,
-  // one CU each -- and a conv-1 grid of more workgroups than the CUs they leave then runs its last
-  // round short of them: the catalogue step (M = 1,344) measured 0.497 ms with the signal against
-  // 0.470-0.475 with the event, which those kernels reach only once conv 1 holds its CUs.
+  // poll are resident before conv 1 starts, one CU each, and a conv-1 grid of more workgroups than the
+  // CUs they leave runs its last round short of them (measured slower: DESIGN.md §4.7, round 7).
   constexpr long kCUs = 256;  // MI355X
   const bool conv1_leaves_cus = conv_fwd_blocks(1, kMels, st_hidden(&p->model.dims), b0.n_items) +
                                     user_fwd_blocks(b0.n_rows) + 1 <= kCUs;
   const bool start_dev =
       dev && xq_edge_on(XQ_START) && p->launches > 0 && ahead && !prologue_first && conv1_leaves_cus;
-  DevWait start_wait{};
-  if (start_dev) start_wait = DevWait{p->sig + kSigStart, ++p->sig_issued[kSigStart], user_fwd_fail_flag()};
-  hipEvent_t ev_in = nullptr;
-  if (!start_dev) TRY(fork_point(sp, s, &ev_in));
+  Edge start;
+  if (start_dev)
+    start.sig = next_signal(p->sig, p->sig_issued, kSigStart);
+  else
+    TRY(fork_point(sp, s, &start.ev));
   // The next step's inputs (slot nxt) are made on wgrad stream 0, which split plans never join back
   // into the caller's stream: the prologue (draws, copy counts, cleared accumulators, published
   // batch) and the lookahead (the announced next batch's bn0 sums and, on the f32 path, its xhat0),
   // issued on the side-issue thread (side.hip) when it runs. The caller's stream waits for them
-  // (inputs_ready) inside this step's backward, just before the conv-1 weight gradient -- long after
+  // (`ready`) inside this step's backward, just before the conv-1 weight gradient -- long after
   // they finished -- so the next launch's conv 1 is ordered after them.
   // DCUE_AHEAD_AT=fork: the lookahead at the backward's first dgrad fork point instead of right
   // behind the prologue (A/B).
-  static const bool ahead_at_fork = [] {
-    const char* e = getenv("DCUE_AHEAD_AT");
-    return e && e[0] == 'f';
-  }();
+  static const bool ahead_at_fork = env_is(getenv("DCUE_AHEAD_AT"), 'f');
   p->ahead_items[nxt] = nullptr;
   const bool look = p->next_items && p->xh[nxt];
   if (look) p->ahead_items[nxt] = p->next_items;
   p->next_items = nullptr;
-  p->inputs_ready = ring_event(sp);  // slot nxt's inputs, for the next launch (recorded below)
-  // the lookahead, then the inputs_ready record, on wgrad stream 0 after `after`
-  DevWait in_sig{};
-  if (dev) in_sig = DevWait{p->sig + kSigInputs, ++p->sig_issued[kSigInputs], user_fwd_fail_flag()};
-  const std::function<int(hipEvent_t)> lookahead = [p, sa, nxt, look, ir = p->inputs_ready, in_sig](hipEvent_t after) -> int {
+  // slot nxt's inputs, for this step's conv-1 weight gradient (so the next launch): recorded -- and
+  // signalled -- behind the lookahead on wgrad stream 0, after `after`
+  Edge ready;
+  ready.ev = ring_event(sp);
+  if (dev) ready.sig = next_signal(p->sig, p->sig_issued, kSigInputs);
+  const std::function<int(hipEvent_t)> lookahead = [p, sa, nxt, look, ready](hipEvent_t after) -> int {
     if (look) {
       if (after) TRY(wait_point(sa, after));
       TRY(debug_delay(DCUE_SITE_LOOKAHEAD, sa));
       TRY(ahead_item_inputs(&p->model, &p->batch, &p->tracks, p->ahead_items[nxt], p->counts[nxt], p->acc[nxt],
                             p->xh[nxt], sa));
     }
-    DCUE_HIP_CHECK(hipEventRecord(ir, sa));
-    if (in_sig.flag) TRY(launch_signal(const_cast<unsigned*>(in_sig.flag), in_sig.val, sa));
+    DCUE_HIP_CHECK(hipEventRecord(ready.ev, sa));
+    if (ready.dev()) TRY(launch_signal(const_cast<unsigned*>(ready.sig.flag), ready.sig.val, sa));
     return DCUE_OK;
   };
   SideQueue side;
   int sst = DCUE_OK;
   uint64_t iseq = 0;
   StepOpts o;
-  o.ev_in = ev_in;
+  o.start = start;
   o.sync_bn = p->sync_bn ? p->comm : nullptr;
   o.prologue_done = true;
   o.fuse_score = true;
@@ -224,20 +215,17 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   o.xhat0 = ahead ? p->xh[cur] : nullptr;
   o.clear_bn0 = prepared && !ahead;
   o.tails = p->tails;
-  o.wait_late = p->late_done;  // the previous split step's late Adam (before conv 1 or 2, late_wait_at_conv1)
+  o.late = p->late_done;  // the previous split step's late Adam (before conv 1 or 2, late_wait_at_conv1)
   o.dense_split = dense_split;
   if (dense_split) o.y1 = p->y1[cur];
   o.comm = dense_split ? p->comm : nullptr;  // the exchange inside the backward (comm_exchange_split)
-  hipEvent_t late_done = nullptr;
+  Edge late_done;
   o.late_done = &late_done;
-  DevWait late_sig{};
   if (dev) {
     o.sig = p->sig;
     o.sig_issued = p->sig_issued;
-    o.late_wait = p->late_sig;
-    o.late_sig = &late_sig;
-    o.inputs_wait = in_sig;
-    o.start_wait = start_wait;
+  } else {
+    o.late.sig = DevWait{};
   }
   // the previous step's rolling-flush slice runs after this step's user tower (StepOpts)
   const bool deferred = p->model.emb_step != nullptr;
@@ -245,10 +233,7 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   o.defer_flush_slice = deferred && emb_adam != nullptr;
   // DCUE_SCORE_FORK=1: the score kernel binds a fork point that the user tower's backward waits for
   // (A/B; default: it waits for the dgrad chain's first fork point, one bound event fewer)
-  static const bool score_fork = [] {
-    const char* e = getenv("DCUE_SCORE_FORK");
-    return e && e[0] == '1';
-  }();
+  static const bool score_fork = env_is(getenv("DCUE_SCORE_FORK"), '1');
   hipEvent_t score_done = nullptr;
   if (score_fork) o.score_done = &score_done;
   auto post_prologue = [&]() -> int {
@@ -265,23 +250,23 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
     // Slot nxt was last read by the previous step, partly on side streams that the caller's stream
     // does not join (split plans): the layer-2 weight gradient on wgrad stream 1 reads its copy
     // counts, BN sums and value ranges, which this prologue clears and rewrites. The previous step's
-    // late Adam waited for every side stream, so its point (late_done, also what this step's conv 2
+    // late Adam waited for every side stream, so its point (p->late_done, also what this step's conv 2
     // waits for) orders the prologue after all of them. Without this wait a delayed layer-2 weight
     // gradient read a cleared range -- a NaN operand scale -- and the step's conv-2 gradient went
     // non-finite (tests/test_gpu_races.py).
-    // (steady state, start_dev: both orders inside the prologue kernel -- the start word and the
-    // late Adam's signal word, the value the previous launch issued into it)
-    hipEvent_t prev_late = legacy_orders() ? nullptr : p->late_done;
-    if (start_dev) {
-      q.wait[0] = start_wait;
-      if (prev_late && p->late_sig.flag) {
-        q.wait[1] = p->late_sig;
-        prev_late = nullptr;
+    // The prologue kernel polls signals itself (q.wait[]). Not the late edge's own choice: its signal
+    // (the value the previous launch issued) is taken only in the steady state, beside the start
+    // signal; a step that starts with an event waits for the late Adam's event too
+    Edge after[2] = {start, legacy_orders() || !p->late_done.ev ? Edge{} : p->late_done};
+    if (!start.dev()) after[1].sig = DevWait{};
+    for (int i = 0; i < 2; ++i)
+      if (after[i].dev()) {
+        q.wait[i] = after[i].sig;
+        after[i] = Edge{};
       }
-    }
-    iseq = side.run([q, sa, ev_in, prev_late, &lookahead]() -> int {
-      if (ev_in) TRY(wait_point(sa, ev_in));
-      if (prev_late) TRY(wait_point(sa, prev_late));
+    iseq = side.run([q, sa, a0 = after[0], a1 = after[1], &lookahead]() -> int {
+      const Edge ev[2] = {a0, a1};
+      TRY(wait_edges(sa, ev, 2));
       TRY(debug_delay(DCUE_SITE_PROLOGUE, sa));
       TRY(launch_step_prologue(q, sa));
       return ahead_at_fork ? DCUE_OK : lookahead(nullptr);  // (the prologue on sa orders it)
@@ -295,14 +280,12 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
   // then issues first
   if (!prologue_first) TRY(post_prologue());
   if (ahead_at_fork) o.ahead = &lookahead;
-  o.wait_inputs = p->inputs_ready;
+  o.inputs = ready;
   o.wait_inputs_seq = iseq;
-  p->inputs_ready = nullptr;
   TRY(backward_impl(&p->model, &b, &p->tracks, p->ws, p->ws_bytes, nullptr, p->cfg.emb_grad_scale, o, s));
   HPROF("plan:5");
   p->pending_flush = o.defer_flush_slice ? emb_adam->step : -1;
-  p->late_done = dense_split ? late_done : nullptr;
-  p->late_sig = dense_split ? late_sig : DevWait{};
+  p->late_done = dense_split ? late_done : Edge{};
   p->last_stream = s;
   ++p->launches;
   return DCUE_OK;
@@ -311,7 +294,7 @@ int issue_eager(dcue_plan* p, const int64_t* users_src, const int32_t* items_src
 int capture(const dcue_model* m, const dcue_batch* b, const dcue_tracks* t, void* ws, size_t ws_bytes,
             const dcue_plan_config* cfg, hipStream_t cs) {
   dcue::capturing_step() = true;
-  const int st = issue_step(m, b, t, ws, ws_bytes, cfg, nullptr, nullptr, cs, nullptr, /*captured=*/true);
+  const int st = issue_step(m, b, t, ws, ws_bytes, cfg, nullptr, nullptr, cs);
   dcue::capturing_step() = false;
   return st;
 }

@@ -112,10 +112,7 @@ class SideIssuer {
 };
 
 bool side_thread_on() {
-  static const bool on = [] {
-    const char* e = getenv("DCUE_SIDE_THREAD");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = !env_is(getenv("DCUE_SIDE_THREAD"), '0');
   return on;
 }
 

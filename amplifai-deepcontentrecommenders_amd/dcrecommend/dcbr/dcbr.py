@@ -6,8 +6,8 @@ regression targets of a ConvNet over the item's mel-spectrogram, trained with th
 error; at inference the ConvNet predicts factors for songs without usage data.
 
 The ConvNet is this repository's DCUE item tower (any of the four wired model types, any width in
-1..256) and the step is one C-ABI call, `dcue_dcbr_step` (capi.hip): the item tower's train
-forward, the MSE head (tail.hip `k_mse_grad`) and the item tower's backward -- the same kernels as
+1..256) and the step is one C-ABI call, `dcue_dcbr_step` (capi.hip; the schedule it issues is in
+step_forward.hip and step_backward.hip): the item tower's train forward, the MSE head (tail.hip `k_mse_grad`) and the item tower's backward -- the same kernels as
 the DCUE step, with the user tower and the scores left out. `NativeAdam` then steps the parameters.
 The reference never published this path (`.gitignore:13`), so parity is unpinned against it; the
 tests pin the step against the fp64 oracle item tower with an MSE head.

@@ -4,7 +4,8 @@ steps without an announced next batch, and batches staged into reused device buf
 on the caller's stream.
 
 Run as a script it makes the runs named on the command line in this process -- the parent sets
-DCUE_XQ_WAIT=event, which the library reads once at load -- and saves them to a file:
+DCUE_XQ_WAIT=event, or one of the group switches DCUE_XQ_START / DCUE_XQ_FORK / DCUE_XQ_LATE to 0,
+which the library reads once at load -- and saves them to a file:
 
   python step_signal_worker.py OUT.pt bn,cat,text,small,nonext
 """
@@ -111,7 +112,9 @@ def main():
     out_path, names = sys.argv[1], sys.argv[2].split(",")
     res = {n: run(**CASES[n]) for n in names}
     torch.save(res, out_path)
-    print(json.dumps({"xq_wait": os.environ.get("DCUE_XQ_WAIT", ""), "fail_flags": int(nat.debug_fail_flags()),
+    print(json.dumps({"xq_wait": os.environ.get("DCUE_XQ_WAIT", ""),
+                      "xq_groups": {g: os.environ.get("DCUE_XQ_" + g, "") for g in ("START", "FORK", "LATE")},
+                      "fail_flags": int(nat.debug_fail_flags()),
                       "finite": {n: finite(r) for n, r in res.items()}}))
     return 0
 
