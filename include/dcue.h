@@ -651,6 +651,9 @@ int dcue_timer_samples(int32_t kernel, float* ms_host, int64_t cap, int64_t* lau
  * Exact tie-aware AUC (Mann-Whitney, ties 1/2) and step-wise AP from integer rank counts, fp64.
  * At most 4096 positives per query inside the lists (else DCUE_ERR_UNSUPPORTED). query_batch
  * queries are scored per pass; the workspace holds their [query_batch][n_cand] score rows.
+ * auc, ap and has_pos do not depend on query_batch, bit for bit: a score is one dot product in a
+ * summation order that depends on d alone, the counts are integers, and the fp64 sums of a query
+ * run in one fixed order.
  * Synchronises `stream` before returning. */
 #define DCUE_RANK_SPLIT 0
 #define DCUE_RANK_SINGLE 1
