@@ -175,6 +175,10 @@ TOPK_FLAG_NO_TRUTH, TOPK_FLAG_BAD_INDEX = 1, 2
 MMR_REL_RAW, MMR_REL_MINMAX = 0, 1
 MMR_RELS = {"raw": MMR_REL_RAW, "minmax": MMR_REL_MINMAX}
 LIST_FLAG_NO_PAIR, LIST_FLAG_BAD_INDEX, LIST_FLAG_NONFINITE = 1, 2, 4
+# dcue_list_explain (added under ABI 17): DCUE_EXPLAIN_MAX_REASONS, DCUE_EXPLAIN_FLAG_NO_HISTORY (bits 1 and 2:
+# LIST_FLAG_BAD_INDEX / LIST_FLAG_NONFINITE)
+EXPLAIN_MAX_REASONS = 8
+EXPLAIN_FLAG_NO_HISTORY = 1
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd", "dgrad_4", "dgrad_3")
@@ -281,6 +285,10 @@ _SIGS = {
     "dcue_list_ild": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
                        _P, ctypes.c_size_t, _P, _P, _P], ctypes.c_int),
     "dcue_list_ild_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P], ctypes.c_int),
+    "dcue_list_explain_workspace_bytes": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_list_explain": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64,
+                           ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P], ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),

@@ -226,6 +226,31 @@ class WRMF:
         return tk.topk(self.user_factors, cand, np.asarray(users, dtype=np.int64).reshape(-1), k,
                        diversity=diversity, pool=pool)
 
+    def explain(self, users, k=10, reasons=3, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
+                pool=None):
+        """recommend()'s lists with the reason for every pick: (idx, score, count) as recommend() returns
+        them (the same dcue_topk_scored call) plus why_idx int64 [n, k, reasons] / why_sim float32
+        [n, k, reasons] -- per pick the `reasons` (1..8) items of the user's by_user row nearest to it by
+        the cosine of the candidate factors, the score similar_items reports for the pair (include/dcue.h
+        dcue_list_explain, on the device lists); short rows end in -1 / -inf. The candidate table must
+        have the fit's items."""
+        reasons = rank.check_reasons(reasons)
+        cand = self._candidates(item_factors)
+        if cand.shape[0] != self.item_factors.shape[0]:
+            raise ValueError("explain needs a candidate table with the fit's %d items" % self.item_factors.shape[0])
+        users = np.asarray(users, dtype=np.int64).reshape(-1)
+        tk = self._topk(exclude_seen, cand_mask, int(cand.shape[0]))
+        idx, score, count, flags = tk.topk_raw(self.user_factors, cand, users, k, diversity=diversity, pool=pool)
+        bad = (flags.cpu().numpy() & 2).astype(bool)
+        if bad.any():
+            raise tk._nonfinite(users, bad)
+        if "explain" not in self._serve:
+            self._serve["explain"] = rank.Explain(self.device)
+        why_idx, why_sim, eflags = self._serve["explain"].explain_raw(idx, count, users, *self._seen(), cand, reasons)
+        rank.check_explain_flags(users, eflags)
+        return (idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy(),
+                why_idx.cpu().numpy().astype(np.int64), why_sim.cpu().numpy())
+
     def similar_items(self, items, k=10):
         """The k items most similar to each item row, by the cosine of the item factors (dcue_topk, as
         DCUE.similar_songs), each item excluded from its own list; same return as recommend()."""

@@ -758,6 +758,55 @@ class DCUE(Trainer):
                                                          diversity=diversity, pool=pool)
         return self._as_pairs(ds, *out) if as_ids else out
 
+    def _explained(self, tk, ds, query_feat, rows, k, reasons, diversity, pool, hist_ptr, hist_idx, as_ids):
+        """tk.topk's lists for `rows` plus dcue_list_explain's reasons over the history CSR, on the lists
+        while they are on the device; the non-finite and bad-index checks of both calls."""
+        feat = self._item_feat_by_index()
+        idx, score, count, flags = tk.topk_raw(query_feat, feat, rows, k, diversity=diversity, pool=pool)
+        bad = (flags.cpu().numpy() & 2).astype(bool)
+        if bad.any():
+            raise tk._nonfinite(rows, bad)
+        if "explain" not in self._evals:
+            self._evals["explain"] = rank.Explain(self.device)
+        why_idx, why_sim, eflags = self._evals["explain"].explain_raw(
+            idx, count, rows, hist_ptr, hist_idx, feat, reasons, hist_mask=(self._item_meta >= 0).astype(np.uint8))
+        rank.check_explain_flags(rows, eflags)
+        idx, score, count = idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
+        why_idx, why_sim = why_idx.cpu().numpy().astype(np.int64), why_sim.cpu().numpy()
+        if not as_ids:
+            return idx, score, count, why_idx, why_sim
+        names = self._index_source(ds).itemindex2songid
+        return [[(names[int(idx[r, j])], float(score[r, j]),
+                  [(names[int(h)], float(s)) for h, s in zip(why_idx[r, j], why_sim[r, j]) if h >= 0])
+                 for j in range(count[r])] for r in range(len(count))]
+
+    def explain(self, users, k=10, reasons=3, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None):
+        """recommend()'s lists with the reason for every pick: per user a list of (song_id, score,
+        [(history_song_id, similarity), ...]) triples -- the picks and scores are recommend()'s, bit for
+        bit (the same dcue_topk call), and the `reasons` (1..8) history songs are those of the user's
+        interactions in any split that have audio, by the cosine of the item factors: the score
+        similar_songs reports for the pair (include/dcue.h dcue_list_explain, one launch on the device
+        lists). A user without such a song gets empty reason lists. as_ids=False: the raw (idx [n, k],
+        score [n, k], count [n], why_idx [n, k, reasons], why_sim [n, k, reasons]) arrays over item
+        indices, short rows ending in -1 / -inf. diversity / pool: as recommend()."""
+        reasons = rank.check_reasons(reasons)
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        src = self._index_source(ds)
+        if not hasattr(src, "user_item_csr"):
+            raise RuntimeError("explain needs the interactions: pass dataset= (any split's dataset holds the "
+                               "all-split matrix) or fit() first")
+        rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
+        tk = self._topk("user", ds, exclude_seen)
+        if exclude_seen and src is (ds if ds is not None else self.train_data):
+            hist = (tk.excl_ptr, tk.excl_idx)  # the CSR _topk already uploaded
+        else:
+            key = ("history", id(src))
+            if key not in self._evals:
+                self._evals[key] = rank._upload_csr(*src.user_item_csr(), self.device)
+            hist = self._evals[key]
+        return self._explained(tk, ds, self.user_factors, rows, k, reasons, diversity, pool, *hist, as_ids)
+
     def similar_songs(self, songs, k=10, dataset=None):
         """The k songs most similar to each song id (item-to-item on the same kernel: the item factors
         on both sides, each song excluded from its own list); same return as recommend()."""
@@ -993,6 +1042,26 @@ class DCUE(Trainer):
         out = rank.TopK(ptr, idx, self._cand_mask(ds), self.device).topk(
             feat, self._item_feat_by_index(), np.arange(len(full)), k, diversity=diversity, pool=pool)
         return self._as_pairs(ds, *out) if as_ids else out
+
+    def explain_for(self, histories, k=10, reasons=3, dataset=None, exclude_history=True, as_ids=True, diversity=None,
+                    pool=None, **fold_in_kwargs):
+        """recommend_for() with the reason for every pick: the lists are recommend_for()'s (the same
+        fold-in and dcue_topk calls), the reasons the `reasons` (1..8) songs of each given history that
+        have audio, nearest to the pick by the cosine of the item factors. Returns what explain() returns."""
+        reasons = rank.check_reasons(reasons)
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        usable, full = self._history_items(histories, ds)
+        args = dict(steps=30, n_neg=None, lr=None, max_pos=64, seed=0, init=None)
+        unknown = set(fold_in_kwargs) - set(args)
+        if unknown:
+            raise TypeError("explain_for() got unexpected fold_in arguments %s" % sorted(unknown))
+        args.update(fold_in_kwargs)
+        feat = self._fold_in(usable, ds, **args)[1]
+        ptr, idx = rank.histories_csr(full) if exclude_history else (None, None)
+        tk = rank.TopK(ptr, idx, self._cand_mask(ds), self.device)
+        return self._explained(tk, ds, feat, np.arange(len(full)), k, reasons, diversity, pool,
+                               *rank.histories_csr(usable), as_ids)
 
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):
         """nn/dcue.py:580-603."""

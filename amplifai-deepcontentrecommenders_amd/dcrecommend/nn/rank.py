@@ -15,6 +15,9 @@ HitRate at several cutoffs and catalogue coverage against held-out truth rows, o
 Diversify (dcue_list_mmr / dcue_list_ild) trades relevance against redundancy: Maximal Marginal Relevance
 re-ranking of TopK's device lists, and their intra-list diversity next to TopKMetrics' numbers.
 
+Explain (dcue_list_explain) says why a song is in a list: for every pick, the songs of the user's
+history nearest to it by the cosine similar_songs reports, on the same device lists.
+
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
@@ -423,6 +426,86 @@ class Diversify(_Workspace):
                                                nat.ptr(mean), nat.ptr(n_eval), nat.stream_handle(self.device)),
                   "dcue_list_ild_mean")
         return mean, n_eval
+
+
+def check_reasons(reasons):
+    """`reasons` as an int in 1..EXPLAIN_MAX_REASONS; ValueError naming the limit otherwise."""
+    m = int(reasons)
+    if not 1 <= m <= nat.EXPLAIN_MAX_REASONS:
+        raise ValueError("reasons must be in 1..%d, got %d" % (nat.EXPLAIN_MAX_REASONS, m))
+    return m
+
+
+def check_explain_flags(queries, flags):
+    """Raises for the first flagged list of an explain call: IndexError for an index out of range
+    (nat.LIST_FLAG_BAD_INDEX), ValueError in the evaluator's wording for a NaN or infinite similarity
+    (nat.LIST_FLAG_NONFINITE). flags: the call's int32 [n] tensor or array."""
+    flags = flags.cpu().numpy() if torch.is_tensor(flags) else np.asarray(flags)
+    bad = (flags & nat.LIST_FLAG_BAD_INDEX).astype(bool)
+    if bad.any():
+        raise IndexError("list, history or query index out of range (query %d)"
+                         % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+    bad = (flags & nat.LIST_FLAG_NONFINITE).astype(bool)
+    if bad.any():
+        raise _nonfinite_error(queries, bad)
+
+
+class Explain(_Workspace):
+    """"Because you played X" for the lists dcue_topk / dcue_list_mmr leave on the device (include/dcue.h
+    dcue_list_explain): per pick, the songs of the query row's history with the largest cosine to it --
+    the very score TopK reports for the pair -- in one kernel launch, no list copied to the host."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def explain_raw(self, idx, count, queries, hist_ptr, hist_idx, cand_feat, m, hist_mask=None):
+        """(why_idx int32 [n, k, m], why_sim float32 [n, k, m], flags int32 [n]) device tensors for the
+        lists idx int32 [n, k] / count int32 [n] (as dcue_topk writes them) of the query rows `queries`.
+        hist_ptr / hist_idx: a CSR over query rows in dcue_topk's exclusion format (arrays, or tensors
+        already on the device); hist_mask [n_cand] uint8 (None: every entry counts): 0 keeps a song out
+        of every history. Short rows end in -1 / -inf. flags: nat.EXPLAIN_FLAG_NO_HISTORY /
+        LIST_FLAG_BAD_INDEX (the list is all padding) / LIST_FLAG_NONFINITE (no check is made here:
+        check_explain_flags raises for them)."""
+        m = check_reasons(m)
+        nat.require_gpu(idx, "idx")
+        nat.require_gpu(count, "count")
+        nat.require_gpu(cand_feat, "cand_feat")
+        if idx.dim() != 2 or idx.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() != idx.shape[0]:
+            raise ValueError("idx must be int32 [n, k] and count int32 [n]")
+        if not 1 <= idx.shape[1] <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, idx.shape[1]))
+        if cand_feat.dim() != 2 or cand_feat.shape[0] < 1 or not 1 <= cand_feat.shape[1] <= 256:
+            raise ValueError("candidate factors must be [n_cand, d] with d in 1..256, got %s"
+                             % (tuple(cand_feat.shape),))
+        idx, count, cand_feat = idx.contiguous(), count.contiguous(), cand_feat.contiguous().float()
+        if torch.is_tensor(queries):
+            q = queries.to(self.device, torch.int32).contiguous().reshape(-1)
+        else:
+            q = torch.as_tensor(np.asarray(queries, dtype=np.int32).reshape(-1)).to(self.device)
+        n, k, n_cand, d = int(idx.shape[0]), int(idx.shape[1]), int(cand_feat.shape[0]), int(cand_feat.shape[1])
+        if q.numel() != n:
+            raise ValueError("%d queries for %d lists" % (q.numel(), n))
+        n_rows = int(hist_ptr.numel() if torch.is_tensor(hist_ptr) else len(hist_ptr)) - 1
+        if n_rows < 1:
+            raise ValueError("the history CSR has no row")
+        ptr, hidx = _upload_csr(hist_ptr, hist_idx, self.device)
+        mask = None
+        if hist_mask is not None:
+            mask = (hist_mask if torch.is_tensor(hist_mask)
+                    else torch.from_numpy(np.ascontiguousarray(hist_mask, dtype=np.uint8)))
+            mask = mask.to(self.device, torch.uint8).contiguous()
+            if mask.numel() != n_cand:
+                raise ValueError("the history mask has %d bytes for %d candidates" % (mask.numel(), n_cand))
+        why_idx = torch.full((max(n, 1), k, m), -1, dtype=torch.int32, device=self.device)
+        why_sim = torch.full((max(n, 1), k, m), float("-inf"), dtype=torch.float32, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        if n:
+            ws = self._grow(self._nbytes("dcue_list_explain_workspace_bytes", n_cand, d, n, k, m))
+            nat.check(nat.lib().dcue_list_explain(
+                nat.ptr(idx), nat.ptr(count), n, k, nat.ptr(q), nat.ptr(ptr), nat.ptr(hidx), n_rows, nat.ptr(mask),
+                nat.ptr(cand_feat), n_cand, d, m, nat.ptr(ws), ws.numel(), nat.ptr(why_idx), nat.ptr(why_sim),
+                nat.ptr(flags), nat.stream_handle(self.device)), "dcue_list_explain")
+        return why_idx[:n], why_sim[:n], flags[:n]
 
 
 class TopKMetrics(_Workspace):

@@ -937,6 +937,49 @@ int dcue_list_ild(const int32_t* idx, const int32_t* count, int32_t n_lists, int
 int dcue_list_ild_mean(const double* ild, const int32_t* flags, int32_t n_lists, int32_t n_cutoffs,
                        double* out_mean /* [m] */, int32_t* out_n_evaluated, void* stream);
 
+/* ------------------------------------------- explained lists: nearest history songs (added under ABI 17) */
+/* "Because you played X": for every pick of the lists dcue_topk / dcue_topk_scored / dcue_list_mmr leave
+ * on the device, the songs of the user's history most similar to it. The reference has no counterpart.
+ * List. idx [n_lists][k] / count [n_lists]: those calls' out_idx / out_count, 1 <= k <= DCUE_TOPK_MAX_K;
+ *   list q is L[0..c), c = count clamped to 0..k. Entries at j >= c are never read.
+ * History. u = queries[q] is the list's query row; hist_ptr [n_query_rows + 1] / hist_idx is a CSR over
+ *   query rows in dcue_topk's exclusion format (candidate indices, each row sorted, no repeats). H_u =
+ *   the row's entries h whose byte hist_mask[h] (hist_mask [n_cand], nullable: every entry) is non-zero
+ *   -- the mask keeps songs without audio, whose factor rows are zero, out. A row may be any length.
+ * Similarity. sim(a, h) = dcue_topk's cosine of rows a and h of cand_feat [n_cand][d], d <= 256, bit for
+ *   bit: x / max(||x||, 1e-8) on each side, zero-padded to the next multiple of 16, summed in dcue_topk's
+ *   order with row a as the query and row h as the candidate. A reason's similarity is the score an
+ *   item-to-item dcue_topk call reports for the pair, whatever else shares the launch.
+ * Reasons. For every position j < c, a = L[j]: the members h of H_u whose sim(a, h) is not NaN, by
+ *   similarity descending, then candidate index ascending (dcue_topk's total order); the first m go to
+ *   out_idx[q][j][0..m) / out_sim[q][j][0..m), 1 <= m <= DCUE_EXPLAIN_MAX_REASONS. Short rows end in
+ *   index -1 / similarity -inf; rows j >= c are all padding. A pick that is itself in H_u is kept.
+ * Flags. out_flags[q] bit 0 (DCUE_EXPLAIN_FLAG_NO_HISTORY): H_u is empty, the list is all padding. Bit 1
+ *   (DCUE_LIST_FLAG_BAD_INDEX): queries[q] lies outside [0, n_query_rows), or an entry L[j], j < c, or an
+ *   entry of the history row lies outside [0, n_cand) -- each is range-checked before it addresses
+ *   anything, the mask included; the list is all padding and the flags are this bit alone. Bit 2
+ *   (DCUE_LIST_FLAG_NONFINITE): a similarity of the list is NaN or infinite; a NaN is never returned,
+ *   everything else stands (dcue_topk's rule).
+ * Invariance. A list's outputs are a function of the list, its history row and the rows they name: they
+ *   do not depend on n_lists, on batching, on which other lists share the launch, or on where the row
+ *   sits inside hist_idx, bit for bit.
+ * dcue_list_explain_workspace_bytes is a host computation: the workspace holds the candidate table's unit
+ * rows, [n_cand][d rounded up to 16] floats. The call is asynchronous on `stream` and validates every
+ * argument on the host before its first device call (DCUE_ERR_INVALID: a null required pointer, k
+ * outside 1..DCUE_TOPK_MAX_K, m outside 1..DCUE_EXPLAIN_MAX_REASONS, n_cand <= 0, d <= 0, n_query_rows <=
+ * 0, n_lists < 0; DCUE_ERR_UNSUPPORTED: d > 256, n_cand beyond dcue_topk's bound; DCUE_ERR_WORKSPACE).
+ * n_lists == 0 is DCUE_OK. */
+#define DCUE_EXPLAIN_MAX_REASONS 8
+#define DCUE_EXPLAIN_FLAG_NO_HISTORY 1 /* bits 1 and 2: DCUE_LIST_FLAG_BAD_INDEX / DCUE_LIST_FLAG_NONFINITE */
+int dcue_list_explain_workspace_bytes(int64_t n_cand, int32_t d, int32_t n_lists, int32_t k, int32_t m,
+                                      size_t* bytes_host);
+int dcue_list_explain(const int32_t* idx, const int32_t* count, int32_t n_lists, int32_t k,
+                      const int32_t* queries, const int64_t* hist_ptr, const int32_t* hist_idx,
+                      int64_t n_query_rows, const uint8_t* hist_mask, const float* cand_feat, int64_t n_cand,
+                      int32_t d, int32_t m, void* ws, size_t ws_bytes,
+                      int32_t* out_idx /* [n_lists][k][m] */, float* out_sim /* [n_lists][k][m] */,
+                      int32_t* out_flags /* [n_lists] */, void* stream);
+
 /* ------------------------------------------- audio front end: waveform -> log-mel (added under ABI 17) */
 /* The step before the item tower: mono f32 waveforms in, [frame][DCUE_N_MELS] track-table rows out, in
  * one launch -- framing, window, FFT, power, mel filterbank and compression fused; no spectrum goes to

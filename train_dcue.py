@@ -12,6 +12,8 @@ this is that driver for the MI355X build:
   python train_dcue.py ... --eval-k 10,50,100 --eval-out metrics.json     # + top-K ranking metrics
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-diversity 0.7
                                                   # MMR re-ranked lists (--recommend-pool: the pool)
+  python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-reasons 3 --reasons-out why.csv
+                                                  # + each pick's 3 nearest songs of the user's history
   python train_dcue.py ... --eval-k 10,50 --eval-out metrics.json --eval-ild --eval-diversity 0.7
                                                   # + intra-list diversity, of the MMR re-ranked lists
 
@@ -70,6 +72,11 @@ def parse(argv=None):
                          "(DCUE.recommend(diversity=L)); default: the plain ranking")
     ap.add_argument("--recommend-pool", type=int, metavar="P",
                     help="candidates ranked per user before the MMR pass (K..128; default min(128, 4 K))")
+    ap.add_argument("--recommend-reasons", type=int, metavar="M",
+                    help="with --recommend-k: for every pick the M (1..8) songs of the user's history nearest to "
+                         "it by the item factors' cosine (DCUE.explain / explain_for), written to --reasons-out")
+    ap.add_argument("--reasons-out", help="CSV for --recommend-reasons: user_id, rank, song_id, reason_rank, "
+                                          "reason_song_id, similarity")
     ap.add_argument("--eval-k", metavar="K[,K...]",
                     help="after training, Precision / Recall / NDCG / MAP / MRR / HitRate / coverage at these "
                          "cutoffs over the val and the test split (DCUE.evaluate_topk)")
@@ -122,6 +129,12 @@ def parse(argv=None):
         ap.error("--recommend-diversity / --recommend-pool need --recommend-k")
     if args.recommend_pool is not None and args.recommend_diversity is None:
         ap.error("--recommend-pool needs --recommend-diversity")
+    if (args.recommend_reasons is not None) != bool(args.reasons_out):
+        ap.error("--recommend-reasons and --reasons-out go together")
+    if args.recommend_reasons is not None and args.recommend_k <= 0:
+        ap.error("--recommend-reasons / --reasons-out need --recommend-k")
+    if args.recommend_reasons is not None and not 1 <= args.recommend_reasons <= 8:
+        ap.error("--recommend-reasons must be in 1..8, got %r" % args.recommend_reasons)
     if (args.eval_ild or args.eval_diversity is not None) and not args.eval_k:
         ap.error("--eval-ild / --eval-diversity need --eval-k")
     for name in ("recommend_diversity", "eval_diversity"):
@@ -194,10 +207,12 @@ def main(argv=None):
             histories = {u: list(g) for u, g in new.groupby("user_id", sort=False)["song_id"]}
             write_recommendations(dcue, list(histories), args.recommend_k, args.recommend_out,
                                   histories=histories, seed=args.seed, diversity=args.recommend_diversity,
-                                  pool=args.recommend_pool)
+                                  pool=args.recommend_pool, reasons=args.recommend_reasons,
+                                  reasons_path=args.reasons_out)
         else:
             write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out,
-                                  diversity=args.recommend_diversity, pool=args.recommend_pool)
+                                  diversity=args.recommend_diversity, pool=args.recommend_pool,
+                                  reasons=args.recommend_reasons, reasons_path=args.reasons_out)
     if args.eval_k:
         write_metrics(dcue, val, test, args.eval_k, args.eval_out, diversity=args.eval_diversity, ild=args.eval_ild)
     return dcue
@@ -215,13 +230,26 @@ def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False):
         f.write("\n")
 
 
-def write_recommendations(dcue, users, k, path, histories=None, seed=0, diversity=None, pool=None):
+def write_recommendations(dcue, users, k, path, histories=None, seed=0, diversity=None, pool=None, reasons=None,
+                          reasons_path=None):
     """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank).
     histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for).
-    diversity / pool: MMR re-ranked lists (DCUE.recommend)."""
+    diversity / pool: MMR re-ranked lists (DCUE.recommend). reasons / reasons_path: also each pick's
+    `reasons` nearest history songs (DCUE.explain / explain_for), one row per (user, rank, reason_rank)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
-    if histories is not None:
+    if reasons is not None:
+        if histories is not None:
+            lists = dcue.explain_for([histories[u] for u in users], k=k, reasons=reasons, seed=seed,
+                                     diversity=diversity, pool=pool)
+        else:
+            lists = dcue.explain(users, k=k, reasons=reasons, diversity=diversity, pool=pool)
+        why = [(u, r + 1, song, j + 1, h, sim) for u, lst in zip(users, lists)
+               for r, (song, _, because) in enumerate(lst) for j, (h, sim) in enumerate(because)]
+        pd.DataFrame(why, columns=["user_id", "rank", "song_id", "reason_rank", "reason_song_id",
+                                   "similarity"]).to_csv(reasons_path, index=False)
+        lists = [[(song, score) for song, score, _ in lst] for lst in lists]
+    elif histories is not None:
         lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed, diversity=diversity, pool=pool)
     else:
         lists = dcue.recommend(users, k=k, diversity=diversity, pool=pool)
