@@ -137,6 +137,13 @@ class CropConfig(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("seed", ctypes.c_uint64), ("draw", ctypes.c_uint64)]
 
 
+class AugmentConfig(ctypes.Structure):
+    """dcue_augment_config (augmentation inside the crop launch, added under ABI 17)."""
+    _fields_ = [("n_freq", ctypes.c_int32), ("freq_width", ctypes.c_int32), ("n_time", ctypes.c_int32),
+                ("time_width", ctypes.c_int32), ("gain_db", ctypes.c_float), ("fill_mode", ctypes.c_int32),
+                ("fill_value", ctypes.c_float), ("reserved", ctypes.c_int32)]
+
+
 class WeightTables(ctypes.Structure):
     """dcue_weight_tables (dcue_sample_catalogue_weighted, added under ABI 17): device uint32 arrays."""
     _fields_ = [(n, ctypes.c_void_p) for n in ("cum", "user_key", "user_skip", "user_weight")]
@@ -145,6 +152,8 @@ class WeightTables(ctypes.Structure):
 CROP_FIRST, CROP_CENTER, CROP_GRID, CROP_RANDOM = 0, 1, 2, 3  # DCUE_CROP_*
 CROP_FLAG_BAD_EXTENT, CROP_FLAG_BAD_ROW = 1, 2
 CROP_FACTOR_DRAW0 = 1 << 32  # the item-factor passes' draws: 2^32 + j, apart from every epoch's
+AUG_MAX_MASKS = 4  # DCUE_AUG_MAX_MASKS
+AUG_FILL_MEAN, AUG_FILL_CONST = 0, 1  # DCUE_AUG_FILL_*
 LOGMEL_POWER, LOGMEL_DB, LOGMEL_LOG1P = 0, 1, 2  # DCUE_LOGMEL_*
 LOGMEL_MODES = {"power": LOGMEL_POWER, "db": LOGMEL_DB, "log1p": LOGMEL_LOG1P}
 LOGMEL_FLAG_NONFINITE = 1
@@ -313,6 +322,11 @@ _SIGS = {
     "dcue_crop_tracks": ([ctypes.POINTER(TrackStore), ctypes.POINTER(CropConfig), _P, ctypes.c_int64, _P,
                           ctypes.c_int32, _P, _P, _P], ctypes.c_int),
     "dcue_crop_starts_host": ([ctypes.POINTER(CropConfig), _P, _P, ctypes.c_int64, _P], ctypes.c_int),
+    "dcue_crop_tracks_augmented": ([ctypes.POINTER(TrackStore), ctypes.POINTER(CropConfig),
+                                    ctypes.POINTER(AugmentConfig), _P, ctypes.c_int64, _P, ctypes.c_int32, _P, _P, _P],
+                                   ctypes.c_int),
+    "dcue_augment_params_host": ([ctypes.POINTER(CropConfig), ctypes.POINTER(AugmentConfig), _P, _P, ctypes.c_int64,
+                                  _P, _P, _P], ctypes.c_int),
     "dcue_debug_delay": ([ctypes.c_int32, ctypes.c_int32], ctypes.c_int),
     "dcue_debug_probes": ([_P], ctypes.c_int),
     "dcue_debug_probe_count": ([], ctypes.c_int),
@@ -356,7 +370,7 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
-        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_resample")):  # the calls that leave a dcue_last_error text
+        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_augment", "dcue_resample")):  # the calls that leave a dcue_last_error text
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 
@@ -588,9 +602,20 @@ def track_store(data, frame_ptr):
                       0 if data.dtype == torch.float16 else 1, 0)
 
 
-def crop_tracks(data, frame_ptr, cfg, out, rows=None, starts=None, flags=None, stream=None):
+def augment_config(freq_masks=0, freq_width=0, time_masks=0, time_width=0, gain_db=0.0, fill="mean"):
+    """dcue_augment_config (include/dcue.h has the rule): fill is 'mean' or the constant a masked
+    element becomes. The library checks the ranges."""
+    mean = isinstance(fill, str)
+    if mean and fill != "mean":
+        raise ValueError("augment: fill must be 'mean' or a number, got %r" % (fill,))
+    return AugmentConfig(int(freq_masks), int(freq_width), int(time_masks), int(time_width), float(gain_db),
+                         AUG_FILL_MEAN if mean else AUG_FILL_CONST, 0.0 if mean else float(fill), 0)
+
+
+def crop_tracks(data, frame_ptr, cfg, out, rows=None, starts=None, flags=None, stream=None, augment=None):
     """dcue_crop_tracks: out [n_out][131][128] (fp16 / fp32) receives the window of track rows[i] (int32;
-    None: track i) of the store (data, frame_ptr). Returns the flags tensor (int32 [n_out], device)."""
+    None: track i) of the store (data, frame_ptr). Returns the flags tensor (int32 [n_out], device).
+    augment (an augment_config): dcue_crop_tracks_augmented, the same windows masked and gain-shifted."""
     n_out = int(out.shape[0])
     if out.dim() != 3 or tuple(out.shape[1:]) != (N_FRAMES, N_MELS) or not out.is_contiguous():
         raise ValueError("crop_tracks: out must be a contiguous [n][%d][%d]" % (N_FRAMES, N_MELS))
@@ -599,9 +624,13 @@ def crop_tracks(data, frame_ptr, cfg, out, rows=None, starts=None, flags=None, s
     if flags is None:
         flags = torch.empty(max(n_out, 1), dtype=torch.int32, device=out.device)
     store = track_store(data, frame_ptr)
-    check(lib().dcue_crop_tracks(ctypes.byref(store), ctypes.byref(cfg), ptr(rows), n_out, ptr(out),
-                                 0 if out.dtype == torch.float16 else 1, ptr(starts), ptr(flags),
-                                 stream_handle(out.device) if stream is None else stream), "dcue_crop_tracks")
+    tail = (n_out, ptr(out), 0 if out.dtype == torch.float16 else 1, ptr(starts), ptr(flags),
+            stream_handle(out.device) if stream is None else stream)
+    if augment is None:
+        check(lib().dcue_crop_tracks(ctypes.byref(store), ctypes.byref(cfg), ptr(rows), *tail), "dcue_crop_tracks")
+    else:
+        check(lib().dcue_crop_tracks_augmented(ctypes.byref(store), ctypes.byref(cfg), ctypes.byref(augment), ptr(rows),
+                                               *tail), "dcue_crop_tracks_augmented")
     return flags[:n_out]
 
 
@@ -648,3 +677,21 @@ def crop_starts_host(cfg, lengths, track_ids=None):
                                       None if ids is None else ctypes.c_void_p(ids.ctypes.data), len(lengths),
                                       ctypes.c_void_p(out.ctypes.data)), "dcue_crop_starts_host")
     return out
+
+
+def augment_params_host(cfg, augment, lengths, track_ids=None):
+    """dcue_augment_params_host: what the augmentation rule gives tracks of `lengths` frames at store
+    indices `track_ids` (default 0..n-1): (gain float32 [n], freq_pw int32 [n][4][2], time_pw int32
+    [n][4][2]), the masks as (place, width). No GPU needed."""
+    import numpy as np
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    ids = None if track_ids is None else np.ascontiguousarray(track_ids, dtype=np.int64)
+    n = len(lengths)
+    gain = np.zeros(n, dtype=np.float32)
+    freq_pw = np.zeros((n, AUG_MAX_MASKS, 2), dtype=np.int32)
+    time_pw = np.zeros((n, AUG_MAX_MASKS, 2), dtype=np.int32)
+    check(lib().dcue_augment_params_host(ctypes.byref(cfg), ctypes.byref(augment), ctypes.c_void_p(lengths.ctypes.data),
+                                         None if ids is None else ctypes.c_void_p(ids.ctypes.data), n,
+                                         ctypes.c_void_p(gain.ctypes.data), ctypes.c_void_p(freq_pw.ctypes.data),
+                                         ctypes.c_void_p(time_pw.ctypes.data)), "dcue_augment_params_host")
+    return gain, freq_pw, time_pw

@@ -21,6 +21,8 @@ stream on the GPU; every DataLoader iteration's torch draws are mirrored), so a 
 the reference's trajectory: tests/golden/fit.npz.
 """
 import ctypes
+import dataclasses
+import math
 import os
 import warnings
 
@@ -132,13 +134,28 @@ def _mt_to_numpy(mt):
     np.random.set_state(("MT19937", buf[:624].copy(), int(buf[624]), 0, 0.0))
 
 
+@dataclasses.dataclass
+class Augment:
+    """DCUE(augment=...): SpecAugment-style masks and a loudness jitter applied while the training table
+    is re-cut (include/dcue.h dcue_crop_tracks_augmented has the rule). Up to 4 frequency masks of at
+    most freq_width mel bins and 4 time masks of at most time_width frames per track, a gain drawn from
+    [-gain_db, gain_db) per track; fill: what a masked element becomes, 'mean' (the window's mean) or a
+    number."""
+    freq_masks: int = 0
+    freq_width: int = 0
+    time_masks: int = 0
+    time_width: int = 0
+    gain_db: float = 0.0
+    fill: object = 'mean'
+
+
 class DCUE(Trainer):
 
     def __init__(self, feature_dim=100, conv_hidden=128, batch_size=64, neg_batch_size=20, u_embdim=300,
                  margin=0.2, optimize='adam', lr=0.00001, beta_one=0.9, beta_two=0.99, eps=1e-8,
                  weight_decay=0, restart_period=30, t_mult=2, num_epochs=90, model_type='truedcuemel1dbn',
                  eval_pct=0.025, val_pct=1.0, device=None, defer_embedding=True, crop='load', crop_seed=0,
-                 factor_crops='random', neg_pool=None, neg_hard=None):
+                 factor_crops='random', neg_pool=None, neg_hard=None, augment=None):
         """Arguments as nn/dcue.py:47-50; device (default cuda:current) and defer_embedding (the
         bit-identical deferred user-table Adam, dcrecommend.optim.NativeAdam) are MI355X additions.
 
@@ -152,8 +169,14 @@ class DCUE(Trainer):
         sub-epochs: every row draws P candidates where it drew N, and keeps the neg_hard (default N // 2;
         0 <= neg_hard <= N) that the factors of the last sub-epoch score highest for its user, filled up
         to N with the pool's leading other draws (include/dcue.h dcue_select_negatives). None, the
-        default, is the plain sampler. Validation and test losses always use N plain draws."""
+        default, is the plain sampler. Validation and test losses always use N plain draws.
+
+        augment (an Augment or a dict of its fields; crop='epoch' only) masks and gain-shifts the windows
+        of the training sub-epochs' re-crop, from (crop_seed, nn_epoch) like the windows themselves.
+        Validation losses, the item factors and embed_audio always see the clean windows. None, the
+        default, is the plain re-crop."""
         self._check_neg_pool(neg_pool, neg_hard)
+        augment = self._check_augment(augment, crop)
         if crop not in ('load', 'epoch'):
             raise ValueError("crop must be 'load' or 'epoch', got %r" % (crop,))
         if factor_crops not in ('random', 'grid'):
@@ -162,6 +185,9 @@ class DCUE(Trainer):
         self.crop = crop
         self.crop_seed = int(crop_seed)
         self.factor_crops = factor_crops
+        self.augment = augment    # None, or the Augment's fields as a plain dict (a checkpoint keeps it)
+        self._tracks_dirty = False  # the table holds augmented windows, cut at draw _tracks_draw
+        self._tracks_draw = 0
         self.neg_pool = None if neg_pool is None else int(neg_pool)
         self.neg_hard = None if neg_hard is None else int(neg_hard)
         self._on_negatives = None  # tests: called as (step, users, pool, negs, hard) on the sampling stream
@@ -272,18 +298,74 @@ class DCUE(Trainer):
         self._item_meta = meta
         self._tracks_src = item_dataset
 
-    def _recrop(self, draw=None):
+    def _recrop(self, draw=None, augment=False):
         """crop='epoch': cut the whole track table again, in place, into the buffer the plan is bound
         to -- a random window of every track from (crop_seed, draw), draw = nn_epoch by default, the
         same on every rank. Returns the call's flags (device). Only at an epoch boundary: the plan must
         hold no lookahead (it would feed the next step statistics of the old rows), and this stream
-        first waits for what the last step left on the plan's side streams, which read the table."""
+        first waits for what the last step left on the plan's side streams, which read the table.
+
+        augment=True (the training sub-epoch's re-crop alone) applies self.augment in the same launch
+        and leaves the table marked dirty: _clean_tracks cuts the same windows again, clean."""
         data, frame_ptr = self._store
         if self._plan is not None:
             self._plan.require_no_lookahead()
             self._plan.sync(nat.stream_handle(self.device))
-        cfg = nat.crop_config(nat.CROP_RANDOM, seed=self.crop_seed, draw=self.nn_epoch if draw is None else draw)
-        return nat.crop_tracks(data, frame_ptr, cfg, self._tracks)
+        draw = self.nn_epoch if draw is None else draw
+        cfg = nat.crop_config(nat.CROP_RANDOM, seed=self.crop_seed, draw=draw)
+        if not augment or self.augment is None:  # exactly the call there was before there was an augment
+            flags = nat.crop_tracks(data, frame_ptr, cfg, self._tracks)
+            self._tracks_dirty = False
+        else:
+            flags = nat.crop_tracks(data, frame_ptr, cfg, self._tracks, augment=nat.augment_config(**self.augment))
+            a = self.augment  # an augment that is off runs the plain kernel: nothing to undo
+            self._tracks_dirty = bool(a["freq_masks"] * a["freq_width"] or a["time_masks"] * a["time_width"]
+                                      or a["gain_db"])
+        self._tracks_draw = draw
+        return flags
+
+    def _clean_tracks(self):
+        """Before anything outside the training sub-epoch reads the table: if it holds augmented windows,
+        cut the same windows -- the same (crop_seed, draw) -- again without the augmentation. A table
+        that is clean already is left alone, so an evaluation after an evaluation re-cuts nothing."""
+        if self._store is not None and self._tracks_dirty:
+            self._recrop(draw=self._tracks_draw)
+
+    @staticmethod
+    def _check_augment(augment, crop):
+        """ValueError for an augment no re-crop could run with. Returns the fields as a plain dict, or
+        None with the augmentation off."""
+        if augment is None:
+            return None
+        if isinstance(augment, Augment):
+            augment = dataclasses.asdict(augment)
+        elif not isinstance(augment, dict):
+            raise ValueError("augment must be an Augment or a dict of its fields, got %r" % (augment,))
+        names = [f.name for f in dataclasses.fields(Augment)]
+        unknown = sorted(set(augment) - set(names))
+        if unknown:
+            raise ValueError("augment: unknown fields %s (known: %s)" % (", ".join(unknown), ", ".join(names)))
+        a = dataclasses.asdict(Augment(**augment))
+        for name, top in (("freq_masks", nat.AUG_MAX_MASKS), ("freq_width", nat.N_MELS),
+                          ("time_masks", nat.AUG_MAX_MASKS), ("time_width", nat.N_FRAMES)):
+            v = a[name]
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= top:
+                raise ValueError("augment: %s must be an integer in 0..%d, got %r" % (name, top, v))
+            a[name] = int(v)
+        try:
+            a["gain_db"] = float(a["gain_db"])
+        except (TypeError, ValueError):
+            raise ValueError("augment: gain_db must be a number, got %r" % (a["gain_db"],))
+        if not (math.isfinite(a["gain_db"]) and a["gain_db"] >= 0):
+            raise ValueError("augment: gain_db must be finite and >= 0, got %r" % (a["gain_db"],))
+        if a["fill"] != 'mean':
+            if isinstance(a["fill"], (str, bool)) or not isinstance(a["fill"], (int, float, np.number)) \
+                    or not math.isfinite(a["fill"]):
+                raise ValueError("augment: fill must be 'mean' or a finite number, got %r" % (a["fill"],))
+            a["fill"] = float(a["fill"])
+        if crop != 'epoch':
+            raise ValueError("augment needs crop='epoch': with crop=%r there is no store to re-cut" % (crop,))
+        return a
 
     @staticmethod
     def _check_neg_pool(neg_pool, neg_hard, N=None):
@@ -355,7 +437,7 @@ class DCUE(Trainer):
         if self._store is not None:
             # before the sampling stream joins the main one below: every later reader of the table --
             # the steps and the lookaheads they start -- is ordered after this stream's re-crop
-            self._recrop()
+            self._recrop(augment=True)
         users_all, items_all = self._rows(ds)
         batches = list(loader)  # the loader's RNG draws happen when its iteration starts, as before
         dev = self.device
@@ -432,6 +514,7 @@ class DCUE(Trainer):
     def _eval_epoch(self, loader):
         """nn/dcue.py:220-262: eval-mode loss over the val set in order (last batch partial)."""
         _loader_draws(1)  # DataLoader(shuffle=False): its iterator's base seed
+        self._clean_tracks()  # the validation loss is computed on the windows as recorded
         self.model.eval()
         ds = _dataset(loader)
         neg = self._negatives(ds)
@@ -490,6 +573,8 @@ class DCUE(Trainer):
                   self.margin, self.optimize, self.lr, self.weight_decay, self.restart_period, self.t_mult,
                   self.num_epochs, self.model_type, n_users, n_items, triplets_path, metadata_path, save_dir),
               flush=True)
+        if self.augment is not None:
+            print(" Augment: {}".format(", ".join("%s=%s" % kv for kv in self.augment.items())), flush=True)
         self.epoch_size = int(int(np.ceil(len(train_dataset) / 10)) // self.batch_size) * self.batch_size
         self.n_users, self.n_items = n_users, n_items
         self.triplets_path, self.metadata_path = triplets_path, metadata_path
@@ -1109,7 +1194,7 @@ class DCUE(Trainer):
                 "lr", "beta_one", "beta_two", "eps", "weight_decay", "restart_period", "t_mult", "num_epochs",
                 "model_type", "eval_pct", "val_pct", "n_users", "n_items", "epoch_size", "nn_epoch",
                 "best_val_map", "best_val_auc", "best_val_loss", "metadata_path", "triplets_path", "model_dir",
-                "defer_embedding", "crop", "crop_seed", "factor_crops", "neg_pool", "neg_hard")
+                "defer_embedding", "crop", "crop_seed", "factor_crops", "neg_pool", "neg_hard", "augment")
     _TENSORS = ("item_factors", "user_factors", "best_item_factors", "best_user_factors")
 
     def _checkpoint(self):
@@ -1143,6 +1228,8 @@ class DCUE(Trainer):
                 setattr(self, k, ck[k])
         if "crop" not in ck:  # a checkpoint from before the per-epoch crops: the table cut once, at load
             self.crop, self.crop_seed, self.factor_crops = 'load', 0, 'random'
+        if "augment" not in ck or self.crop != 'epoch':  # a checkpoint from before the augmentation: none
+            self.augment = None
         self._init_nn()
         self.model.load_state_dict(ck["model"])
         for k in self._TENSORS:

@@ -1155,6 +1155,69 @@ int dcue_crop_tracks(const dcue_track_store* store, const dcue_crop_config* cfg,
 int dcue_crop_starts_host(const dcue_crop_config* cfg, const int64_t* lengths_host,
                           const int64_t* track_ids_host, int64_t n, int64_t* starts_host);
 
+/* ----------------------------- augmentation inside the crop launch (added under ABI 17) */
+/* dcue_crop_tracks_augmented is dcue_crop_tracks with SpecAugment-style masks (Park et al. 2019), a
+ * loudness jitter and a fill, applied while the window is copied: no further pass over the table. Like
+ * the window, what a track gets is a function of (configuration, track index, track length) alone --
+ * not of the output row, the launch, the batch or the rank.
+ * Configuration. dcue_augment_config: 0 <= n_freq, n_time <= DCUE_AUG_MAX_MASKS (4) masks of each kind,
+ *   their largest widths 0 <= freq_width (F) <= 128 mel bins and 0 <= time_width (T) <= 131 frames;
+ *   gain_db (G) >= 0 and finite, the half-range of the jitter; fill_mode DCUE_AUG_FILL_MEAN or
+ *   DCUE_AUG_FILL_CONST with the finite constant fill_value; reserved is zero. The augmentation is off
+ *   when n_freq * freq_width == 0, n_time * time_width == 0 and gain_db == 0.
+ * Hash streams. h is DCUE_CROP_RANDOM's hash of (seed, draw, t) above, computed whatever cfg->mode is,
+ *   and r(i) = mix(h + G64 * (i + 1)) modulo 2^64, mix and G64 = 0x9E3779B97F4A7C15 as above. The gain
+ *   uses r(0); frequency mask j uses r(1 + 2j) for its width and r(2 + 2j) for its place; time mask j
+ *   uses r(9 + 2j) and r(10 + 2j) -- 9 = 1 + 2 * DCUE_AUG_MAX_MASKS, so the time masks stay where they
+ *   are when n_freq changes.
+ * Masks. n = min(L, 131) is the number of valid frames of the row.
+ *   frequency mask  w = mulhi64(r, F + 1), p = mulhi64(r', 128 - w + 1): mel bins [p, p + w) of every
+ *                   valid frame.
+ *   time mask       w = min(mulhi64(r, T + 1), n), p = mulhi64(r', n - w + 1): frames [p, p + w).
+ *   A row's mask is the union of its masks. The zero tail of a short track is never touched, and a
+ *   track with L = 0 stays all zero.
+ * Gain. One value g per track, in fp32, every operation rounded to nearest even and none contracted:
+ *   u24 = r(0) >> 40, g = gain_db * (float(u24) * 2^-23 - 1.0f) -- the product is the only rounding --
+ *   so g lies in [-G, G).
+ * Elements. A valid element x (the store's value widened to fp32, which is exact) becomes x + g (one
+ *   fp32 add) when it is not masked, and the fill when it is; the result is converted to out_dtype by
+ *   the conversion above (exact, or round to nearest even). With gain_db == 0 no add happens: the source
+ *   bits go through exactly as in dcue_crop_tracks.
+ * Fill. CONST: fill_value; the gain does not apply to it. MEAN: m + g (m when gain_db == 0), m the mean
+ *   of the row's n * 128 valid source elements, each first rounded to fp16 (nothing to do for an fp16
+ *   store). The sum S is exact integer arithmetic: finite fp16 values are integer multiples of 2^-24
+ *   of magnitude at most 65,504, so 16,768 of them, in units of 2^-24, fit an int64; then
+ *   m = float32(double(S) * 2^-24 / double(n * 128)), and m is NaN if one of the rounded elements is
+ *   not finite. So the fill does not depend on how a row is split into parts, on the reduction tree
+ *   or on the launch shape.
+ * dcue_crop_tracks_augmented: the arguments of dcue_crop_tracks plus `aug`. With aug == NULL or an aug
+ *   that is off it runs dcue_crop_tracks' kernel and gives its bits. Flags, starts and the guards are
+ *   dcue_crop_tracks': a flagged row is zeros. Refused on the host before any device call
+ *   (DCUE_ERR_INVALID, with a dcue_last_error text): a count or a width out of range, a negative or
+ *   non-finite gain_db, a non-finite fill_value, an unknown fill_mode, a non-zero reserved, and
+ *   everything dcue_crop_tracks refuses. One launch, no workspace; asynchronous on `stream`.
+ * dcue_augment_params_host: the same integer and fp32 arithmetic on the CPU (no device call) for tracks
+ *   of lengths_host[i] frames at store indices track_ids_host[i] (null: i): gain_host [n] receives g,
+ *   freq_pw_host and time_pw_host (int32 [n][DCUE_AUG_MAX_MASKS][2]) each mask's (place, width), zeros
+ *   for the masks past the count. Each of the three may be null. */
+#define DCUE_AUG_MAX_MASKS 4
+#define DCUE_AUG_FILL_MEAN 0
+#define DCUE_AUG_FILL_CONST 1
+typedef struct dcue_augment_config {
+  int32_t n_freq, freq_width;  /* frequency masks: count, largest width F */
+  int32_t n_time, time_width;  /* time masks: count, largest width T */
+  float gain_db;               /* G */
+  int32_t fill_mode;           /* DCUE_AUG_FILL_* */
+  float fill_value;            /* DCUE_AUG_FILL_CONST */
+  int32_t reserved;
+} dcue_augment_config;
+int dcue_crop_tracks_augmented(const dcue_track_store* store, const dcue_crop_config* cfg,
+                               const dcue_augment_config* aug, const int32_t* rows, int64_t n_out, void* out,
+                               int32_t out_dtype, int32_t* starts, int32_t* flags, void* stream);
+int dcue_augment_params_host(const dcue_crop_config* cfg, const dcue_augment_config* aug,
+                             const int64_t* lengths_host, const int64_t* track_ids_host, int64_t n,
+                             float* gain_host, int32_t* freq_pw_host, int32_t* time_pw_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,7 +105,19 @@ def parse(argv=None):
     ap.add_argument("--neg-hard", type=int, metavar="H",
                     help="DCUE(neg_hard=...), with --neg-pool: hard negatives per row, 0 <= H <= --neg-batch-size "
                          "(default: half of --neg-batch-size)")
+    ap.add_argument("--augment-freq-masks", type=int, metavar="N",
+                    help="DCUE(augment=...), with --crop epoch: frequency masks per track (0..4) applied while the "
+                         "training table is re-cut (dcue_crop_tracks_augmented); val losses and factors stay clean")
+    ap.add_argument("--augment-freq-width", type=int, metavar="F", help="largest width of a frequency mask, in mel bins (0..128)")
+    ap.add_argument("--augment-time-masks", type=int, metavar="N", help="time masks per track (0..4)")
+    ap.add_argument("--augment-time-width", type=int, metavar="T", help="largest width of a time mask, in frames (0..131)")
+    ap.add_argument("--augment-gain-db", type=float, metavar="G",
+                    help="loudness jitter: every track's window is shifted by a gain drawn from [-G, G)")
+    ap.add_argument("--augment-fill", type=_augment_fill, metavar="{mean,<float>}",
+                    help="what a masked element becomes: the window's mean (default) or a constant")
     args = ap.parse_args(argv)
+    if augment_of(args) is not None and args.crop != "epoch":
+        ap.error("--augment-* need --crop epoch")
     if args.neg_alpha < 0:
         ap.error("--neg-alpha must be >= 0, got %r" % args.neg_alpha)
     if args.neg_hard is not None and args.neg_pool is None:
@@ -142,6 +154,22 @@ def parse(argv=None):
         if lam is not None and not 0.0 <= lam <= 1.0:
             ap.error("--%s takes a lambda in [0, 1], got %r" % (name.replace("_", "-"), lam))
     return args
+
+
+def _augment_fill(text):
+    if text == "mean":
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("'mean' or a number, got %r" % text)
+
+
+def augment_of(args):
+    """The --augment-* options that were given, as DCUE(augment=...) takes them; None when none was."""
+    names = ("freq_masks", "freq_width", "time_masks", "time_width", "gain_db", "fill")
+    given = {n: getattr(args, "augment_" + n) for n in names if getattr(args, "augment_" + n) is not None}
+    return given or None
 
 
 def synthetic_data(n_users, n_tracks, n_pairs, out_dir, seed):
@@ -198,7 +226,7 @@ def main(argv=None):
                 weight_decay=args.weight_decay, num_epochs=args.num_epochs, eval_pct=args.eval_pct,
                 val_pct=args.val_pct, optimize=args.optimize, model_type=args.model_type, crop=args.crop,
                 crop_seed=args.crop_seed, factor_crops=args.factor_crops, neg_pool=args.neg_pool,
-                neg_hard=args.neg_hard)
+                neg_hard=args.neg_hard, augment=augment_of(args))
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
     if args.recommend_k > 0 and args.recommend_out:
