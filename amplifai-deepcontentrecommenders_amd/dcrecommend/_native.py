@@ -188,6 +188,10 @@ LIST_FLAG_NO_PAIR, LIST_FLAG_BAD_INDEX, LIST_FLAG_NONFINITE = 1, 2, 4
 # LIST_FLAG_BAD_INDEX / LIST_FLAG_NONFINITE)
 EXPLAIN_MAX_REASONS = 8
 EXPLAIN_FLAG_NO_HISTORY = 1
+# dcue_list_group_cap / dcue_list_group_stats (added under ABI 17): DCUE_GROUP_FLAG_*, DCUE_GROUP_N_STATS (bit 1:
+# LIST_FLAG_BAD_INDEX)
+GROUP_FLAG_SHORT, GROUP_FLAG_BAD_GROUP = 8, 16
+GROUP_N_STATS = 2  # distinct, top
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd", "dgrad_4", "dgrad_3")
@@ -298,6 +302,12 @@ _SIGS = {
                                            ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_list_explain": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64,
                            ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_list_group_cap": ([_P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32,
+                             ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_list_group_stats": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int64, ctypes.c_int32, _P,
+                               ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
+    "dcue_list_group_stats_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, _P, _P],
+                                   ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
@@ -370,7 +380,8 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
-        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_augment", "dcue_resample")):  # the calls that leave a dcue_last_error text
+        if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_augment", "dcue_resample",
+                                         "dcue_list_group")):  # the calls that leave a dcue_last_error text
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 

@@ -79,10 +79,7 @@ class DCUEDataset(Dataset):
         """Song split 80/10/10 (dcuedataset.py:146-164): both masks are drawn right after
         np.random.seed(10), so the global numpy stream is left where the reference leaves it."""
         if self.song_artist_map is not None:
-            # the reference's artist split calls Series.get_values() (dcuedataset.py:112), removed in
-            # pandas 1.0: it cannot run with the pinned pandas either
-            raise NotImplementedError("artist splitting (song_artist_map) is not supported: the "
-                                      "reference path needs pandas < 1.0")
+            return self._split_by_artist()
         songs = self.triplets['song_id'].unique()
         np.random.seed(10)
         in_train = np.random.rand(len(songs)) < 0.80
@@ -100,6 +97,26 @@ class DCUEDataset(Dataset):
         else:
             return
         self.triplets = self.triplets[keep]
+
+    def _split_by_artist(self):
+        """Artist split 70/10/20 (dcuedataset.py:108-143): no artist has songs in two splits. As the
+        reference wrote it: np.random.seed(10), sklearn.utils.shuffle of the unique songs and their
+        artists, GroupShuffleSplit(test_size=0.3) by artist, then GroupShuffleSplit(test_size=0.3333) of
+        the held-out songs, whose larger part is test and whose smaller part is val. Both draw from
+        the global numpy stream. Parity with the reference is UNPINNED: its path calls
+        Series.get_values(), removed in pandas 1.0, so it cannot run and no golden split exists; here
+        the songs come from .to_numpy(). A song without an entry in the map raises KeyError, as there."""
+        from sklearn.model_selection import GroupShuffleSplit
+        from sklearn.utils import shuffle
+        songs = np.asarray(self.triplets['song_id'].unique())
+        artists = np.array([self.song_artist_map[s] for s in songs])
+        np.random.seed(10)
+        songs, artists = shuffle(songs, artists)
+        train, held = next(GroupShuffleSplit(n_splits=1, test_size=0.3).split(songs, groups=artists))
+        test, val = next(GroupShuffleSplit(n_splits=1, test_size=0.3333).split(songs[held], groups=artists[held]))
+        part = {'train': songs[train], 'val': songs[held][val], 'test': songs[held][test]}
+        if self.split in part:
+            self.triplets = self.triplets[self.triplets['song_id'].isin(part[self.split])]
 
     # ------------------------------------------------------------------ reference API
     def _sample(self, X, length, dim=1):

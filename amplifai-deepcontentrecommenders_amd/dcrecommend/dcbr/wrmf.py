@@ -207,7 +207,7 @@ class WRMF:
         return self._serve[key]
 
     def recommend(self, users, k=10, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
-                  pool=None):
+                  pool=None, groups=None, max_per_group=None):
         """The k best items for each user row by x_u . y_i: (idx int64 [n, k], score float32 [n, k],
         count int32 [n]) numpy arrays, best first, short lists padded with -1 / -inf. exclude_seen
         drops the items of the user's by_user row. item_factors [n_cand, factors] (device) replaces
@@ -218,13 +218,27 @@ class WRMF:
         min(128, 4 k)) re-ranked down to k by Maximal Marginal Relevance (dcue_list_mmr) -- the
         inner-product scores min-max scaled per list, the redundancy the cosine of the candidate
         factors, as similar_items measures it. The lists are then in selection order, each entry
-        with its own inner-product score."""
+        with its own inner-product score.
+
+        max_per_group with groups, an int array by candidate row (an item's artist, album, ...; -1: none):
+        no group holds more than that many items of a list (rank.TopK.topk_raw max_per_group=:
+        dcue_list_group_cap on the `pool` best items, short lists ranked deeper; with diversity= the
+        pool is capped before MMR picks from it)."""
         cand = self._candidates(item_factors)
         if exclude_seen and cand.shape[0] != self.item_factors.shape[0]:
             raise ValueError("exclude_seen needs a candidate table with the fit's %d items" % self.item_factors.shape[0])
         tk = self._topk(exclude_seen, cand_mask, int(cand.shape[0]))
         return tk.topk(self.user_factors, cand, np.asarray(users, dtype=np.int64).reshape(-1), k,
-                       diversity=diversity, pool=pool)
+                       diversity=diversity, pool=pool, **self._group_kw(groups, max_per_group))
+
+    @staticmethod
+    def _group_kw(groups, max_per_group):
+        """rank.TopK's group arguments (none without a cap: today's path)."""
+        if max_per_group is None:
+            if groups is not None:
+                raise ValueError("groups goes with max_per_group=, which is not set")
+            return {}
+        return dict(group_of=groups, max_per_group=max_per_group)
 
     def explain(self, users, k=10, reasons=3, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
                 pool=None):
@@ -302,18 +316,20 @@ class WRMF:
         return out
 
     def recommend_for(self, histories, k=10, exclude_history=True, values=None, item_factors=None, cand_mask=None,
-                      diversity=None, pool=None):
+                      diversity=None, pool=None, groups=None, max_per_group=None):
         """recommend() for users outside the fit: fold_in(histories, values), then the inner-product
-        top-k with each history as the user's exclusion row. diversity / pool: as recommend(). Returns
-        what recommend() returns."""
+        top-k with each history as the user's exclusion row. diversity / pool / groups / max_per_group:
+        as recommend(). Returns what recommend() returns."""
         cand = self._candidates(item_factors)
         feat = self.fold_in(histories, values)
         ptr, idx = rank.histories_csr(histories) if exclude_history else (None, None)
         tk = rank.TopK(ptr, idx, self._mask(cand_mask), self.device, n_cand=int(cand.shape[0]), score="dot")
-        return tk.topk(feat, cand, np.arange(len(histories)), k, diversity=diversity, pool=pool)
+        return tk.topk(feat, cand, np.arange(len(histories)), k, diversity=diversity, pool=pool,
+                       **self._group_kw(groups, max_per_group))
 
     def evaluate_topk(self, truth_ptr, truth_idx, ks=(10, 50, 100), users=None, exclude_ptr=None, exclude_idx=None,
-                      item_factors=None, cand_mask=None, per_user=False, diversity=None, pool=None, ild=False):
+                      item_factors=None, cand_mask=None, per_user=False, diversity=None, pool=None, ild=False,
+                      groups=None, max_per_group=None):
         """Top-K ranking quality of the inner-product lists against held-out truth rows (a CSR over
         user rows, each row sorted, no repeats): DCUE.evaluate_topk's dict -- {"precision@K",
         "recall@K", "ndcg@K", "map@K", "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} --
@@ -321,7 +337,10 @@ class WRMF:
         exclude_ptr / exclude_idx: what the lists must not return (the training interactions;
         default none); per_user adds "users", "per_user" and "flags". diversity / pool: score
         recommend(diversity=, pool=)'s MMR re-ranked lists (k = max(ks)) instead; ild adds "ild@K" (the
-        mean intra-list diversity of the scored lists, dcue_list_ild) and "n_ild"."""
+        mean intra-list diversity of the scored lists, dcue_list_ild) and "n_ild". groups (an int array by
+        candidate row) adds "groups@K", "group_top@K" and "group_coverage@K" -- DCUE.evaluate_topk's
+        artist numbers (dcue_list_group_stats) -- and "n_group_lists"; with max_per_group the lists scored
+        are recommend(groups=, max_per_group=)'s."""
         ks = rank.check_cutoffs(ks)
         cand = self._candidates(item_factors)
         ev = rank.TopKMetrics(truth_ptr, truth_idx, self.device, excl_ptr=exclude_ptr, excl_idx=exclude_idx,
@@ -330,9 +349,18 @@ class WRMF:
             rows = np.flatnonzero(np.diff(np.asarray(truth_ptr, dtype=np.int64)) > 0).astype(np.int64)
         else:
             rows = np.asarray(users, dtype=np.int64).reshape(-1)
+        group_kw = {} if groups is None else dict(group_of=groups, group_stats=True)
+        if max_per_group is not None:
+            group_kw.update(self._group_kw(groups, max_per_group))
         res = ev.evaluate(self.user_factors, cand, rows, ks, per_query=per_user, diversity=diversity, pool=pool,
-                          ild=ild)
+                          ild=ild, **group_kw)
         out = {"n_users": res["n_evaluated"]}
+        if groups is not None:
+            for name, slot in (("groups", "group_distinct"), ("group_top", "group_top"),
+                               ("group_coverage", "group_coverage")):
+                for i, k in enumerate(ks):
+                    out["%s@%d" % (name, k)] = float(res[slot][i])
+            out["n_group_lists"] = res["n_group"]
         for name in nat.TOPK_METRIC_NAMES + ("coverage",) + (("ild",) if ild else ()):
             for i, k in enumerate(ks):
                 out["%s@%d" % (name, k)] = float(res[name][i])

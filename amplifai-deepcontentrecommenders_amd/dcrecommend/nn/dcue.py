@@ -31,6 +31,7 @@ import torch
 from torch.utils.data import RandomSampler
 
 from dcrecommend import _native as nat
+from dcrecommend.datasets.artists import artist_exclusion_csr, artist_groups
 from dcrecommend.datasets.csr import (check_catalogue_users, saturated_users, user_split_ranks,
                                       weighted_saturated_users, weighted_split_tables)
 from dcrecommend.dcue.dcue import DCUENet
@@ -239,6 +240,7 @@ class DCUE(Trainer):
         self._plan = None
         self._plan_n = None
         self._evals = {}
+        self._song_artist_map = None  # set_artists
 
     # ------------------------------------------------------------------ model / optimizer
     def _init_nn(self, audio_model=None):
@@ -799,14 +801,20 @@ class DCUE(Trainer):
         shares them (the category codes over all triplets)."""
         return ds if ds is not None else self.train_data if self.train_data is not None else self._tracks_src
 
-    def _topk(self, kind, ds, exclude_seen):
-        """rank.TopK per (kind, dataset, exclude_seen), cached as _evaluator caches its lists."""
-        key = ("topk", kind, id(ds), bool(exclude_seen))
+    def _topk(self, kind, ds, exclude_seen, by_artist=False, with_artist=False):
+        """rank.TopK per (kind, dataset, exclude_seen, by_artist, with_artist), cached as _evaluator caches
+        its lists. by_artist: the exclusion rows also hold every song of the artists behind them
+        (datasets.artists.artist_exclusion_csr) -- the artists a user has played, or a song's own artist.
+        with_artist: only songs with a known artist are candidates."""
+        if not (by_artist or with_artist):
+            key = ("topk", kind, id(ds), bool(exclude_seen))
+        else:
+            key = ("topk", kind, id(ds), bool(exclude_seen), bool(by_artist), bool(with_artist))
         if key not in self._evals:
             mask = self._cand_mask(ds)
             if kind == "song":
                 ptr, idx = rank.identity_csr(len(mask))
-            elif exclude_seen:
+            elif exclude_seen or by_artist:
                 src = ds if ds is not None else self.train_data
                 if src is None:
                     raise RuntimeError("exclude_seen needs the interactions: pass dataset= (any split's "
@@ -814,15 +822,51 @@ class DCUE(Trainer):
                 ptr, idx = src.user_item_csr()
             else:
                 ptr = idx = None
+            if by_artist or with_artist:
+                group_of = self._artist_groups(ds)[0]
+                if with_artist:
+                    mask = mask & (group_of >= 0).astype(np.uint8)
+                if by_artist:
+                    ptr, idx = artist_exclusion_csr(group_of, played=None if kind == "song" else (ptr, idx),
+                                                    seen=(ptr, idx) if kind == "song" or exclude_seen else None)
             self._evals[key] = rank.TopK(ptr, idx, mask, self.device)
         return self._evals[key]
+
+    def set_artists(self, song_artist_map):
+        """Who recorded each song: a {song_id: artist} dict (songs without an entry have no artist and are
+        never capped), read by max_per_artist=, new_artists=, other_artists=, recommend_artists and
+        evaluate_topk(artists=True). Without it the artists are those of the dataset in use, when that
+        was built with song_artist_map. None forgets the artists."""
+        self._song_artist_map = None if song_artist_map is None else dict(song_artist_map)
+        for key in [k for k in self._evals if k[0] == "artists" or (k[0] == "topk" and len(k) > 4)]:
+            del self._evals[key]
+
+    def _artist_groups(self, ds):
+        """(group_of int32 [n_items], artist names) over the item indices of ds (or the training data):
+        datasets.artists.artist_groups, cached per index source."""
+        src = self._index_source(ds)
+        key = ("artists", id(src))
+        if key not in self._evals:
+            amap = self._song_artist_map if self._song_artist_map is not None else getattr(src, "song_artist_map", None)
+            if amap is None:
+                raise RuntimeError("no artists to go by: call set_artists({song_id: artist}) first, or use a "
+                                   "dataset built with song_artist_map")
+            self._evals[key] = artist_groups(src.item_index, amap)
+        return self._evals[key]
+
+    def _cap_kw(self, ds, max_per_artist, cap_rounds=4):
+        """TopK.topk's group arguments for max_per_artist (None: none, today's path)."""
+        if max_per_artist is None:
+            return {}
+        return dict(group_of=self._artist_groups(ds)[0], max_per_group=max_per_artist, cap_rounds=cap_rounds)
 
     def _as_pairs(self, ds, idx, score, count):
         names = self._index_source(ds).itemindex2songid
         return [[(names[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
                 for r in range(len(count))]
 
-    def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None):
+    def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None,
+                  max_per_artist=None, new_artists=False, cap_rounds=4):
         """The k best songs for each user id, by the cosine of DCUE.score: one list per user of
         (song_id, score) pairs, best first (as_ids=False: the raw (idx [n, k], score [n, k],
         count [n]) arrays over item indices). Candidates are the dataset's (or loader's) split songs,
@@ -834,20 +878,46 @@ class DCUE(Trainer):
         diversity (lambda in [0, 1]; None: the plain ranking): the user's `pool` best songs (default
         min(128, 4 k)) re-ranked down to k by Maximal Marginal Relevance over the item factors' cosine
         (dcue_list_mmr): each pick maximises lambda * score - (1 - lambda) * (its largest similarity to
-        the songs picked before it). The lists are then in selection order, each with its own score."""
+        the songs picked before it). The lists are then in selection order, each with its own score.
+
+        max_per_artist (None: no cap; needs set_artists or a dataset with song_artist_map): no artist holds
+        more than that many songs of a list (dcue_list_group_cap on the `pool` best songs; lists the cap
+        leaves short are ranked deeper, at most cap_rounds - 1 times, and then equal the cap applied to
+        the user's full ranking). A list can still come back shorter than k when the rounds or the
+        catalogue run out. With diversity= the pool is capped before MMR picks from it. new_artists: the
+        songs of every artist the user has played in any split are left out, played or not."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         index = self._index_source(ds).user_index
         rows = np.array([index[u] for u in users], dtype=np.int64)
-        out = self._topk("user", ds, exclude_seen).topk(self.user_factors, self._item_feat_by_index(), rows, k,
-                                                         diversity=diversity, pool=pool)
+        cap_kw = self._cap_kw(ds, max_per_artist, cap_rounds)
+        out = self._topk("user", ds, exclude_seen, by_artist=new_artists).topk(
+            self.user_factors, self._item_feat_by_index(), rows, k, diversity=diversity, pool=pool, **cap_kw)
         return self._as_pairs(ds, *out) if as_ids else out
 
-    def _explained(self, tk, ds, query_feat, rows, k, reasons, diversity, pool, hist_ptr, hist_idx, as_ids):
+    def recommend_artists(self, users, k=10, dataset=None, exclude_seen=True, new_artists=False, cap_rounds=4):
+        """The k best ARTISTS for each user id: per user a list of (artist, best_song_id, score) triples,
+        artists ranked by their best eligible song -- recommend(max_per_artist=1) over the songs with a
+        known artist, mapped through the artists' names. Exact when no list comes back short of k (the
+        deepening rounds, cap_rounds - 1 at the most, reached k artists or the end of the catalogue).
+        exclude_seen / new_artists: as recommend()."""
+        self._require_factors()
+        ds = None if dataset is None else _dataset(dataset)
+        src = self._index_source(ds)
+        group_of, names = self._artist_groups(ds)
+        rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
+        idx, score, count = self._topk("user", ds, exclude_seen, by_artist=new_artists, with_artist=True).topk(
+            self.user_factors, self._item_feat_by_index(), rows, k, **self._cap_kw(ds, 1, cap_rounds))
+        songs = src.itemindex2songid
+        return [[(names[int(group_of[i])], songs[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
+                for r in range(len(count))]
+
+    def _explained(self, tk, ds, query_feat, rows, k, reasons, diversity, pool, hist_ptr, hist_idx, as_ids,
+                   cap_kw={}):
         """tk.topk's lists for `rows` plus dcue_list_explain's reasons over the history CSR, on the lists
         while they are on the device; the non-finite and bad-index checks of both calls."""
         feat = self._item_feat_by_index()
-        idx, score, count, flags = tk.topk_raw(query_feat, feat, rows, k, diversity=diversity, pool=pool)
+        idx, score, count, flags = tk.topk_raw(query_feat, feat, rows, k, diversity=diversity, pool=pool, **cap_kw)
         bad = (flags.cpu().numpy() & 2).astype(bool)
         if bad.any():
             raise tk._nonfinite(rows, bad)
@@ -865,7 +935,8 @@ class DCUE(Trainer):
                   [(names[int(h)], float(s)) for h, s in zip(why_idx[r, j], why_sim[r, j]) if h >= 0])
                  for j in range(count[r])] for r in range(len(count))]
 
-    def explain(self, users, k=10, reasons=3, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None):
+    def explain(self, users, k=10, reasons=3, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None,
+                max_per_artist=None, new_artists=False):
         """recommend()'s lists with the reason for every pick: per user a list of (song_id, score,
         [(history_song_id, similarity), ...]) triples -- the picks and scores are recommend()'s, bit for
         bit (the same dcue_topk call), and the `reasons` (1..8) history songs are those of the user's
@@ -873,7 +944,8 @@ class DCUE(Trainer):
         similar_songs reports for the pair (include/dcue.h dcue_list_explain, one launch on the device
         lists). A user without such a song gets empty reason lists. as_ids=False: the raw (idx [n, k],
         score [n, k], count [n], why_idx [n, k, reasons], why_sim [n, k, reasons]) arrays over item
-        indices, short rows ending in -1 / -inf. diversity / pool: as recommend()."""
+        indices, short rows ending in -1 / -inf. diversity / pool / max_per_artist / new_artists: as
+        recommend()."""
         reasons = rank.check_reasons(reasons)
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
@@ -882,25 +954,29 @@ class DCUE(Trainer):
             raise RuntimeError("explain needs the interactions: pass dataset= (any split's dataset holds the "
                                "all-split matrix) or fit() first")
         rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
-        tk = self._topk("user", ds, exclude_seen)
-        if exclude_seen and src is (ds if ds is not None else self.train_data):
+        tk = self._topk("user", ds, exclude_seen, by_artist=new_artists)
+        if exclude_seen and not new_artists and src is (ds if ds is not None else self.train_data):
             hist = (tk.excl_ptr, tk.excl_idx)  # the CSR _topk already uploaded
         else:
             key = ("history", id(src))
             if key not in self._evals:
                 self._evals[key] = rank._upload_csr(*src.user_item_csr(), self.device)
             hist = self._evals[key]
-        return self._explained(tk, ds, self.user_factors, rows, k, reasons, diversity, pool, *hist, as_ids)
+        return self._explained(tk, ds, self.user_factors, rows, k, reasons, diversity, pool, *hist, as_ids,
+                               self._cap_kw(ds, max_per_artist))
 
-    def similar_songs(self, songs, k=10, dataset=None):
+    def similar_songs(self, songs, k=10, dataset=None, max_per_artist=None, other_artists=False, pool=None):
         """The k songs most similar to each song id (item-to-item on the same kernel: the item factors
-        on both sides, each song excluded from its own list); same return as recommend()."""
+        on both sides, each song excluded from its own list); same return as recommend().
+        max_per_artist / pool: as recommend(). other_artists: no song by the query song's own artist is
+        returned ("similar songs, but not by the same artist")."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         index = self._index_source(ds).item_index
         rows = np.array([index[s] for s in songs], dtype=np.int64)
         feat = self._item_feat_by_index()
-        return self._as_pairs(ds, *self._topk("song", ds, True).topk(feat, feat, rows, k))
+        return self._as_pairs(ds, *self._topk("song", ds, True, by_artist=other_artists).topk(
+            feat, feat, rows, k, pool=pool, **self._cap_kw(ds, max_per_artist)))
 
     # ------------------------------------------------------------------ unseen songs
     def embed_audio(self, wave, logmel=None, frame0=0, crops=None, sample_rate=None, resample="best"):
@@ -963,15 +1039,26 @@ class DCUE(Trainer):
                       "dcue_item_tower_eval")
         return feat[:n]
 
-    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None, crops=None, sample_rate=None, resample="best"):
+    def similar_to_audio(self, wave, k=10, dataset=None, logmel=None, crops=None, sample_rate=None, resample="best",
+                         max_per_artist=None, other_artists=False):
         """The k catalogue songs nearest to each clip, by the cosine of its embed_audio factor to the
         item factors: one list of (song_id, score) pairs per clip, as similar_songs returns (nothing is
         excluded: the clip is not in the catalogue). crops: as embed_audio -- the whole song, not its
-        first window. sample_rate / resample: as embed_audio."""
+        first window. sample_rate / resample: as embed_audio. max_per_artist: as recommend().
+        other_artists: False, or one artist name per clip (None: no artist) -- the clip's own artist, whose
+        catalogue songs are then left out of its list."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         q = self.embed_audio(wave, logmel, crops=crops, sample_rate=sample_rate, resample=resample)
-        out = self._topk("audio", ds, False).topk(q, self._item_feat_by_index(), np.arange(q.shape[0]), k)
+        tk = self._topk("audio", ds, False)
+        if other_artists is not False:
+            group_of, names = self._artist_groups(ds)
+            own = list(other_artists)
+            if len(own) != q.shape[0]:
+                raise ValueError("other_artists names %d artists for %d clips" % (len(own), q.shape[0]))
+            tk = rank.TopK(*rank.histories_csr([np.flatnonzero(group_of == names.index(a)) if a in names else []
+                                                for a in own]), self._cand_mask(ds), self.device)
+        out = tk.topk(q, self._item_feat_by_index(), np.arange(q.shape[0]), k, **self._cap_kw(ds, max_per_artist))
         return self._as_pairs(ds, *out)
 
     def listeners_for_audio(self, wave, k=10, logmel=None, crops=None, sample_rate=None, resample="best"):
@@ -1008,7 +1095,7 @@ class DCUE(Trainer):
         return self._evals[key]
 
     def evaluate_topk(self, dataset=None, ks=(10, 50, 100), users=None, per_user=False, diversity=None, pool=None,
-                      ild=False):
+                      ild=False, artists=False, max_per_artist=None):
         """Top-K ranking quality of the current factors: {"precision@K", "recall@K", "ndcg@K", "map@K",
         "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} (include/dcue.h dcue_topk_metrics
         has the definitions). Candidates are the dataset's (or loader's) split songs with audio, or
@@ -1024,7 +1111,13 @@ class DCUE(Trainer):
         diversity / pool: score recommend(diversity=, pool=)'s MMR re-ranked lists (k = max(ks)) instead.
         ild adds "ild@K" -- the mean intra-list diversity (1 - cosine of the item factors, averaged
         over the pairs of a list's first K songs; dcue_list_ild) of the lists that were scored -- and
-        "n_ild", the number of lists behind it."""
+        "n_ild", the number of lists behind it.
+
+        max_per_artist: score recommend(max_per_artist=)'s capped lists. artists adds "artists@K" (the mean
+        number of distinct artists among a list's first K songs, a song without an artist counting as one
+        of its own), "artist_top@K" (the mean of the most songs one artist holds there) and
+        "artist_coverage@K" (the share of the artists with a candidate song that appear in some list's
+        first K), by dcue_list_group_stats on the same device lists, and "n_artist_lists"."""
         ks = rank.check_cutoffs(ks)
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
@@ -1036,12 +1129,21 @@ class DCUE(Trainer):
         else:
             users = list(users)
             rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
+        cap_kw = self._cap_kw(ds, max_per_artist)
+        if artists:
+            cap_kw.update(group_of=self._artist_groups(ds)[0], group_stats=True)
         res = ev.evaluate(self.user_factors, self._item_feat_by_index(), rows, ks, per_query=per_user,
-                          diversity=diversity, pool=pool, ild=ild)
+                          diversity=diversity, pool=pool, ild=ild, **cap_kw)
         out = {"n_users": res["n_evaluated"]}
         for name in nat.TOPK_METRIC_NAMES + ("coverage",) + (("ild",) if ild else ()):
             for i, k in enumerate(ks):
                 out["%s@%d" % (name, k)] = float(res[name][i])
+        if artists:
+            for name, slot in (("artists", "group_distinct"), ("artist_top", "group_top"),
+                               ("artist_coverage", "group_coverage")):
+                for i, k in enumerate(ks):
+                    out["%s@%d" % (name, k)] = float(res[slot][i])
+            out["n_artist_lists"] = res["n_group"]
         if ild:
             out["n_ild"] = res["n_ild"]
         if per_user:
@@ -1110,10 +1212,11 @@ class DCUE(Trainer):
         return emb, feat, loss
 
     def recommend_for(self, histories, k=10, dataset=None, exclude_history=True, as_ids=True, diversity=None,
-                      pool=None, **fold_in_kwargs):
+                      pool=None, max_per_artist=None, new_artists=False, **fold_in_kwargs):
         """recommend() for users outside the trained table: fold_in(histories, **fold_in_kwargs), then
         the fused top-k pass with each history as the user's exclusion list (every song of it, with
-        or without audio). diversity / pool: as recommend(). Returns what recommend() returns."""
+        or without audio). diversity / pool / max_per_artist: as recommend(); new_artists: the songs of
+        every artist in the history are left out. Returns what recommend() returns."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         usable, full = self._history_items(histories, ds)
@@ -1123,13 +1226,22 @@ class DCUE(Trainer):
             raise TypeError("recommend_for() got unexpected fold_in arguments %s" % sorted(unknown))
         args.update(fold_in_kwargs)
         feat = self._fold_in(usable, ds, **args)[1]
-        ptr, idx = rank.histories_csr(full) if exclude_history else (None, None)
+        ptr, idx = self._history_exclusion(ds, full, exclude_history, new_artists)
         out = rank.TopK(ptr, idx, self._cand_mask(ds), self.device).topk(
-            feat, self._item_feat_by_index(), np.arange(len(full)), k, diversity=diversity, pool=pool)
+            feat, self._item_feat_by_index(), np.arange(len(full)), k, diversity=diversity, pool=pool,
+            **self._cap_kw(ds, max_per_artist))
         return self._as_pairs(ds, *out) if as_ids else out
 
+    def _history_exclusion(self, ds, full, exclude_history, new_artists):
+        """The exclusion CSR of recommend_for / explain_for: the histories, and with new_artists every
+        song of their artists; (None, None) for neither."""
+        hist = rank.histories_csr(full)
+        if new_artists:
+            return artist_exclusion_csr(self._artist_groups(ds)[0], played=hist, seen=hist if exclude_history else None)
+        return hist if exclude_history else (None, None)
+
     def explain_for(self, histories, k=10, reasons=3, dataset=None, exclude_history=True, as_ids=True, diversity=None,
-                    pool=None, **fold_in_kwargs):
+                    pool=None, max_per_artist=None, new_artists=False, **fold_in_kwargs):
         """recommend_for() with the reason for every pick: the lists are recommend_for()'s (the same
         fold-in and dcue_topk calls), the reasons the `reasons` (1..8) songs of each given history that
         have audio, nearest to the pick by the cosine of the item factors. Returns what explain() returns."""
@@ -1143,10 +1255,10 @@ class DCUE(Trainer):
             raise TypeError("explain_for() got unexpected fold_in arguments %s" % sorted(unknown))
         args.update(fold_in_kwargs)
         feat = self._fold_in(usable, ds, **args)[1]
-        ptr, idx = rank.histories_csr(full) if exclude_history else (None, None)
+        ptr, idx = self._history_exclusion(ds, full, exclude_history, new_artists)
         tk = rank.TopK(ptr, idx, self._cand_mask(ds), self.device)
         return self._explained(tk, ds, feat, np.arange(len(full)), k, reasons, diversity, pool,
-                               *rank.histories_csr(usable), as_ids)
+                               *rank.histories_csr(usable), as_ids, self._cap_kw(ds, max_per_artist))
 
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):
         """nn/dcue.py:580-603."""

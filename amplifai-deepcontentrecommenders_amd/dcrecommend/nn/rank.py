@@ -18,6 +18,9 @@ re-ranking of TopK's device lists, and their intra-list diversity next to TopKMe
 Explain (dcue_list_explain) says why a song is in a list: for every pick, the songs of the user's
 history nearest to it by the cosine similar_songs reports, on the same device lists.
 
+GroupCap (dcue_list_group_cap / dcue_list_group_stats) knows who made a song: at most so many entries per
+group (artist, album, label) of TopK's device lists, and how many groups a list spans.
+
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
@@ -90,6 +93,9 @@ def _upload_csr(ptr, idx, device):
 
 def _upload_mask(cand_mask, n_cand, device):
     """(uint8 mask on the device, its length), or (None, n_cand) without a mask."""
+    if torch.is_tensor(cand_mask):  # (a mask already on a device)
+        mask = cand_mask.to(device, torch.uint8).contiguous()
+        return mask, int(mask.numel())
     if cand_mask is not None:
         mask = torch.from_numpy(np.ascontiguousarray(cand_mask, dtype=np.uint8)).to(device)
         return mask, int(mask.numel())
@@ -207,6 +213,10 @@ class TopK(_Workspace):
 
     DEFAULT_QUERY_BATCH = 4096
     _div = None  # the Diversify of diversity= calls, made at the first one
+    _gcap = None  # the GroupCap of max_per_group= calls, likewise
+    _groups = None  # (the caller's group_of, its device copy, n_groups) of the last max_per_group= call
+    _excl_np = None  # the exclusion CSR's host copy, for deepening rounds
+    cap_rounds_used = 0  # ranking rounds of the last max_per_group= call (1: no list was deepened)
 
     def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None, score="cosine"):
         self.device = torch.device(device)
@@ -224,20 +234,95 @@ class TopK(_Workspace):
     def _nonfinite(self, queries, bad):
         return (_nonfinite_error if self.score == nat.SCORE_COSINE else _nonfinite_dot_error)(queries, bad)
 
-    def _diverse_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel):
+    def _diverse_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel,
+                     groups=None):
         """topk_raw at k = pool, then Diversify.mmr_raw down to k. The flags are dcue_topk's; a list MMR
-        found non-finite (nat.LIST_FLAG_NONFINITE) carries dcue_topk's bit for it."""
+        found non-finite (nat.LIST_FLAG_NONFINITE) carries dcue_topk's bit for it. groups (_group_args): the
+        pool is capped per group before MMR sees it."""
         k, pool = check_pool(k, pool)
         if rel is None:
             rel = "raw" if self.score == nat.SCORE_COSINE else "minmax"
         if self._div is None:
             self._div = Diversify(self.device)
         idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split)
+        gflags = None
+        if groups is not None:  # MMR picks from a pool that already satisfies the cap, so its output does too
+            idx, score, count, _, gflags = self._cap().cap_raw(idx, score, count, *groups, pool)
         idx, score, count, mflags = self._div.mmr_raw(idx, score, count, cand_feat, k, diversity, rel)
-        return idx, score, count, flags | ((mflags & nat.LIST_FLAG_NONFINITE) >> 1)
+        flags = flags | ((mflags & nat.LIST_FLAG_NONFINITE) >> 1)
+        if gflags is not None:
+            flags = flags | (gflags & nat.GROUP_FLAG_BAD_GROUP) | (count < k).int() * nat.GROUP_FLAG_SHORT
+        return idx, score, count, flags
+
+    def _cap(self):
+        if self._gcap is None:
+            self._gcap = GroupCap(self.device)
+        return self._gcap
+
+    def _group_args(self, group_of, max_per_group, cap_rounds):
+        """(group_of int32 [n_cand] on the device, n_groups, cap) of a max_per_group= call; the uploaded
+        map is kept for the next call with the same array."""
+        if group_of is None:
+            raise ValueError("max_per_group needs group_of, the candidates' groups")
+        cap, cap_rounds = int(max_per_group), int(cap_rounds)
+        if cap < 1:
+            raise ValueError("max_per_group must be at least 1, got %d" % cap)
+        if cap_rounds < 1:
+            raise ValueError("cap_rounds must be at least 1, got %d" % cap_rounds)
+        if self._groups is None or self._groups[0] is not group_of:
+            g = group_of if torch.is_tensor(group_of) else torch.from_numpy(np.ascontiguousarray(group_of, np.int32))
+            g = g.to(self.device, torch.int32).contiguous().reshape(-1)
+            if g.numel() != self.n_cand:
+                raise ValueError("group_of has %d entries for %d candidates" % (g.numel(), self.n_cand))
+            self._groups = (group_of, g, max(int(g.max()) + 1, 0))
+        return self._groups[1], self._groups[2], cap
+
+    def _excl_host(self):
+        """The base exclusion CSR as numpy arrays (None, None without one), copied back once."""
+        if self._excl_np is None and self.excl_ptr is not None:
+            self._excl_np = (self.excl_ptr.cpu().numpy(), self.excl_idx.cpu().numpy())
+        return self._excl_np if self._excl_np is not None else (None, None)
+
+    def _capped_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, pool, groups, cap_rounds):
+        """topk_raw at k = pool, GroupCap.cap_raw down to k, and up to cap_rounds - 1 deepening rounds for
+        the lists the cap left short of k while their pool was full: those lists' query rows are ranked
+        again at k = pool with everything ranked so far added to their exclusion rows -- a score is a
+        function of the two rows and d alone, so this is the next `pool` entries of the same total order
+        -- and the cap continues with the entries kept so far as its carry. A list that comes back
+        without GROUP_FLAG_SHORT equals the cap applied to the full ranking. The deepening CSR is built
+        on the host (the rare path)."""
+        k, pool = check_pool(k, pool)
+        queries = np.asarray(queries, dtype=np.int64).reshape(-1)
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split)
+        gc = self._cap()
+        oidx, oscore, ocount, _, gflags = gc.cap_raw(idx, score, count, *groups, k)
+        self.cap_rounds_used = 1
+        ranked = {}  # list -> every pool entry ranked for it so far
+        for _ in range(int(cap_rounds) - 1):
+            rows = torch.nonzero(((gflags & nat.GROUP_FLAG_SHORT) != 0) & (count == pool)).reshape(-1)
+            if rows.numel() == 0:
+                break
+            self.cap_rounds_used += 1
+            rows_np = rows.cpu().numpy()
+            for r, entries in zip(rows_np, idx.index_select(0, rows).cpu().numpy()):
+                ranked[r] = np.concatenate([ranked[r], entries]) if r in ranked else entries
+            bptr, bidx = self._excl_host()
+            excl = [np.union1d(ranked[r], bidx[bptr[queries[r]]:bptr[queries[r] + 1]]) if bptr is not None
+                    else np.unique(ranked[r]) for r in rows_np]
+            qrows = torch.as_tensor(queries[rows_np]).to(self.device)
+            deeper = TopK(*histories_csr(excl), self.cand_mask, self.device, n_cand=self.n_cand,
+                          score=[s for s, v in nat.SCORES.items() if v == self.score][0])
+            didx, dscore, dcount, dflags = deeper.topk_raw(query_feat.index_select(0, qrows), cand_feat,
+                                                           np.arange(len(rows_np)), pool, query_batch, cand_split)
+            carry = (oidx.index_select(0, rows), oscore.index_select(0, rows), ocount.index_select(0, rows))
+            nidx, nscore, ncount, _, nflags = gc.cap_raw(didx, dscore, dcount, *groups, k, carry=carry)
+            idx[rows], count[rows] = didx, dcount  # the pools the next round continues from
+            oidx[rows], oscore[rows], ocount[rows], gflags[rows] = nidx, nscore, ncount, nflags
+            flags[rows] |= dflags
+        return oidx, oscore, ocount, flags | (gflags & (nat.GROUP_FLAG_SHORT | nat.GROUP_FLAG_BAD_GROUP))
 
     def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
-                 rel=None):
+                 rel=None, group_of=None, max_per_group=None, cap_rounds=4):
         """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
         as dcue_topk writes them (no non-finite check).
 
@@ -245,11 +330,31 @@ class TopK(_Workspace):
         `pool` best candidates are ranked (default min(128, 4 k); k <= pool <= 128) and re-ranked down
         to k by Maximal Marginal Relevance on the device (Diversify.mmr_raw, include/dcue.h
         dcue_list_mmr). rel: "raw" / "minmax" relevance scaling, default raw for cosine scores and
-        minmax for dot. The scores returned are the entries' original ones."""
+        minmax for dot. The scores returned are the entries' original ones.
+
+        max_per_group (None: no cap, today's path exactly) with group_of, an int array [n_cand] of each
+        candidate's group (artist, album, ...; -1: ungrouped, never capped): no group holds more than
+        max_per_group entries of a list (GroupCap.cap_raw, include/dcue.h dcue_list_group_cap). The
+        `pool` best candidates are ranked and capped down to k; lists the cap leaves short while their
+        pool was full are deepened, at most cap_rounds - 1 times (_capped_raw). flags then also carries
+        nat.GROUP_FLAG_SHORT (fewer than k entries: the catalogue or the rounds ran out) and
+        GROUP_FLAG_BAD_GROUP. With diversity= the pool is capped first and MMR picks from the capped pool,
+        without deepening."""
+        if max_per_group is not None:
+            groups = self._group_args(group_of, max_per_group, cap_rounds)
+            if diversity is not None:
+                return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool,
+                                         rel, groups)
+            if rel is not None:
+                raise ValueError("rel belongs to diversity=, which is not set")
+            return self._capped_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, pool, groups,
+                                    cap_rounds)
+        if group_of is not None:
+            raise ValueError("group_of belongs to max_per_group=, which is not set")
         if diversity is not None:
             return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel)
         if pool is not None or rel is not None:
-            raise ValueError("pool and rel belong to diversity=, which is not set")
+            raise ValueError("pool and rel belong to diversity= (pool also to max_per_group=), which is not set")
         nat.require_gpu(query_feat, "query_feat")
         nat.require_gpu(cand_feat, "cand_feat")
         query_feat = query_feat.contiguous().float()
@@ -281,20 +386,23 @@ class TopK(_Workspace):
         return idx[:nq], score[:nq], count[:nq], flags[:nq]
 
     def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
-             rel=None):
+             rel=None, group_of=None, max_per_group=None, cap_rounds=4):
         """(idx int64 [n, k], score float32 [n, k], count int32 [n]) numpy arrays, best first; rows
         with fewer than k eligible candidates end in idx -1 / score -inf. diversity / pool / rel: as
-        topk_raw (the lists are then in MMR's selection order, not sorted by score).
+        topk_raw (the lists are then in MMR's selection order, not sorted by score). group_of /
+        max_per_group / cap_rounds: as topk_raw; a group id outside -1 .. n_groups - 1 raises ValueError.
 
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite: a diverged model fails here as it fails in DCUE.score (score="dot": the factors are
         not finite or the product overflowed)."""
         idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split,
-                                                 diversity, pool, rel)
+                                                 diversity, pool, rel, group_of, max_per_group, cap_rounds)
         flags = flags.cpu().numpy()
         bad = (flags & 2).astype(bool)
         if bad.any():
             raise self._nonfinite(queries, bad)
+        if (flags & nat.GROUP_FLAG_BAD_GROUP).any():
+            raise ValueError("group_of holds a group id below -1")
         return idx.cpu().numpy().astype(np.int64), score.cpu().numpy(), count.cpu().numpy()
 
 
@@ -426,6 +534,155 @@ class Diversify(_Workspace):
                                                nat.ptr(mean), nat.ptr(n_eval), nat.stream_handle(self.device)),
                   "dcue_list_ild_mean")
         return mean, n_eval
+
+
+def check_group_flags(queries, flags):
+    """Raises for the first flagged list of a GroupCap call: IndexError for an index out of range
+    (nat.LIST_FLAG_BAD_INDEX), ValueError for a group id outside -1 .. n_groups - 1
+    (nat.GROUP_FLAG_BAD_GROUP). GROUP_FLAG_SHORT is no error. flags: the call's int32 [n] tensor or array."""
+    flags = flags.cpu().numpy() if torch.is_tensor(flags) else np.asarray(flags)
+    bad = (flags & nat.LIST_FLAG_BAD_INDEX).astype(bool)
+    if bad.any():
+        raise IndexError("list or carried index out of range (query %d)"
+                         % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+    bad = (flags & nat.GROUP_FLAG_BAD_GROUP).astype(bool)
+    if bad.any():
+        raise ValueError("group id outside -1 .. n_groups - 1 (query %d)"
+                         % int(np.asarray(queries).reshape(-1)[int(np.argmax(bad))]))
+
+
+class GroupCap(_Workspace):
+    """Per-group caps and group statistics of the lists dcue_topk / dcue_list_mmr leave on the device
+    (include/dcue.h dcue_list_group_cap / dcue_list_group_stats / dcue_list_group_stats_mean): device
+    tensors in and out, one kernel launch per call, no list is copied to the host. A group is whatever
+    group_of says -- artist, album, label; -1 is "ungrouped"."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+
+    def _lists(self, idx, count, group_of, n_groups, score=None):
+        for t, name in ((idx, "idx"), (count, "count"), (group_of, "group_of")):
+            nat.require_gpu(t, name)
+        if idx.dim() != 2 or idx.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() != idx.shape[0]:
+            raise ValueError("idx must be int32 [n, k] and count int32 [n]")
+        if not 1 <= idx.shape[1] <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, idx.shape[1]))
+        if group_of.dtype != torch.int32 or group_of.dim() != 1 or group_of.numel() < 1:
+            raise ValueError("group_of must be int32 [n_cand]")
+        if not 0 <= int(n_groups) <= 2 ** 31 - 1:
+            raise ValueError("n_groups must be in 0..2^31 - 1, got %d" % n_groups)
+        if score is not None:
+            nat.require_gpu(score, "score")
+            if score.dtype != torch.float32 or score.shape != idx.shape:
+                raise ValueError("score must be float32 %s like idx, got %s %s"
+                                 % (tuple(idx.shape), score.dtype, tuple(score.shape)))
+            score = score.contiguous()
+        return idx.contiguous(), count.contiguous(), group_of.contiguous(), score
+
+    def cap_raw(self, idx, score, count, group_of, n_groups, cap, k_out, carry=None):
+        """(idx int32 [n, k_out], score float32 [n, k_out], count int32 [n], dropped int32 [n], flags int32
+        [n]) device tensors: the pools idx int32 [n, pool] / score float32 [n, pool] / count int32 [n] (as
+        dcue_topk writes them) cut down to at most `cap` entries per group of group_of (int32 [n_cand] on
+        the device), in pool order, k_out at the most. carry: (idx [n, k_out], score [n, k_out], count [n])
+        of entries an earlier call kept -- they come first, unchanged, and count toward their groups.
+        dropped: the pool positions the cap removed before the list filled. flags:
+        nat.LIST_FLAG_BAD_INDEX / GROUP_FLAG_BAD_GROUP (such a list comes back empty) and GROUP_FLAG_SHORT
+        (fewer than k_out entries; they are valid)."""
+        idx, count, group_of, score = self._lists(idx, count, group_of, n_groups, score)
+        n, pool, k_out, cap = int(idx.shape[0]), int(idx.shape[1]), int(k_out), int(cap)
+        if score is None:
+            raise ValueError("score is needed")
+        if cap < 1:
+            raise ValueError("cap must be at least 1, got %d" % cap)
+        if not 1 <= k_out <= nat.TOPK_MAX_K:
+            raise ValueError("k_out must be in 1..%d, got %d" % (nat.TOPK_MAX_K, k_out))
+        cidx = cscore = ccount = None
+        if carry is not None:
+            cidx, cscore, ccount = carry
+            for t, name in ((cidx, "carry idx"), (cscore, "carry score"), (ccount, "carry count")):
+                nat.require_gpu(t, name)
+            if (cidx.dtype != torch.int32 or cscore.dtype != torch.float32 or ccount.dtype != torch.int32
+                    or tuple(cidx.shape) != (n, k_out) or tuple(cscore.shape) != (n, k_out) or ccount.numel() != n):
+                raise ValueError("carry must be (int32 [n, k_out], float32 [n, k_out], int32 [n])")
+            cidx, cscore, ccount = cidx.contiguous(), cscore.contiguous(), ccount.contiguous()
+        out_idx = torch.full((max(n, 1), k_out), -1, dtype=torch.int32, device=self.device)
+        out_score = torch.full((max(n, 1), k_out), float("-inf"), dtype=torch.float32, device=self.device)
+        out_count = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        dropped = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        if n:
+            nat.check(nat.lib().dcue_list_group_cap(
+                nat.ptr(idx), nat.ptr(score), nat.ptr(count), n, pool, nat.ptr(group_of), int(group_of.numel()),
+                int(n_groups), cap, k_out, nat.ptr(cidx), nat.ptr(cscore), nat.ptr(ccount), nat.ptr(out_idx),
+                nat.ptr(out_score), nat.ptr(out_count), nat.ptr(dropped), nat.ptr(flags),
+                nat.stream_handle(self.device)), "dcue_list_group_cap")
+        return out_idx[:n], out_score[:n], out_count[:n], dropped[:n], flags[:n]
+
+    def _stats_into(self, idx, count, group_of, n_groups, ks, cut, out, flags, exposure):
+        """dcue_list_group_stats on checked device lists, writing out [n, m, 2] / flags [n] (views of the
+        caller's buffers) and accumulating into exposure (or None)."""
+        n, k = int(idx.shape[0]), int(idx.shape[1])
+        if ks[-1] > k:
+            raise ValueError("cutoff %d is beyond the lists' k = %d" % (ks[-1], k))
+        if exposure is not None and (exposure.dtype != torch.int32 or tuple(exposure.shape) != (len(ks), n_groups)):
+            raise ValueError("exposure must be int32 [%d, %d]" % (len(ks), n_groups))
+        if n:
+            nat.check(nat.lib().dcue_list_group_stats(
+                nat.ptr(idx), nat.ptr(count), n, k, nat.ptr(group_of), int(group_of.numel()), int(n_groups),
+                ctypes.cast(cut, ctypes.c_void_p), len(ks), nat.ptr(out), nat.ptr(flags), nat.ptr(exposure),
+                nat.stream_handle(self.device)), "dcue_list_group_stats")
+
+    def stats_raw(self, idx, count, group_of, n_groups, ks, exposure=None):
+        """(stats int32 [n, m, 2], flags int32 [n]) device tensors for the lists idx int32 [n, k] / count
+        int32 [n] at the sorted distinct cutoffs of ks: per cutoff K the number of distinct groups among
+        the first min(K, count) entries (each ungrouped entry one of its own) and the most entries one
+        group holds. exposure: an int32 [m, n_groups] device tensor to accumulate into (new_exposure), or
+        None. A flagged list (LIST_FLAG_BAD_INDEX / GROUP_FLAG_BAD_GROUP) has zeros and adds no exposure."""
+        ks = check_cutoffs(ks)
+        cut = (ctypes.c_int32 * len(ks))(*ks)
+        idx, count, group_of, _ = self._lists(idx, count, group_of, n_groups)
+        n = int(idx.shape[0])
+        out = torch.zeros((max(n, 1), len(ks), nat.GROUP_N_STATS), dtype=torch.int32, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        self._stats_into(idx, count, group_of, int(n_groups), ks, cut, out, flags, exposure)
+        return out[:n], flags[:n]
+
+    def new_exposure(self, m, n_groups):
+        return torch.zeros((m, max(int(n_groups), 1)), dtype=torch.int32, device=self.device)[:, :int(n_groups)]
+
+    def mean_raw(self, stats, flags, exposure=None, present=None):
+        """(mean float64 [m, 2], coverage float64 [m] or None, n_evaluated int32 [1]) device tensors:
+        dcue_list_group_stats_mean over stats [n, m, 2] / flags [n] -- exact int64 sums over the unflagged
+        lists and one division each. exposure (int32 [m, n_groups], contiguous): adds the share of groups
+        exposed up to each cutoff among those with a non-zero byte in present (uint8 [n_groups] on the
+        device; None: all groups)."""
+        nat.require_gpu(stats, "stats")
+        nat.require_gpu(flags, "flags")
+        if (stats.dim() != 3 or stats.shape[2] != nat.GROUP_N_STATS or stats.dtype != torch.int32
+                or flags.dtype != torch.int32 or flags.numel() != stats.shape[0]):
+            raise ValueError("stats must be int32 [n, m, 2] and flags int32 [n]")
+        n, m = int(stats.shape[0]), int(stats.shape[1])
+        if not 1 <= m <= nat.TOPK_METRICS_MAX_CUTOFFS:
+            raise ValueError("at most %d cutoffs per call, got %d" % (nat.TOPK_METRICS_MAX_CUTOFFS, m))
+        n_groups = 0
+        if exposure is not None:
+            if exposure.dtype != torch.int32 or exposure.dim() != 2 or exposure.shape[0] != m:
+                raise ValueError("exposure must be int32 [%d, n_groups]" % m)
+            n_groups = int(exposure.shape[1])
+            exposure = exposure.contiguous() if n_groups else torch.zeros((m, 1), dtype=torch.int32, device=self.device)
+            if present is not None and (present.dtype != torch.uint8 or present.numel() != n_groups):
+                raise ValueError("present must be uint8 [%d]" % n_groups)
+        mean = torch.zeros((m, nat.GROUP_N_STATS), dtype=torch.float64, device=self.device)
+        cov = torch.zeros(m, dtype=torch.float64, device=self.device) if exposure is not None else None
+        n_eval = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if n == 0:  # (an empty tensor's address may be null)
+            stats = torch.zeros((1, m, nat.GROUP_N_STATS), dtype=torch.int32, device=self.device)
+            flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().dcue_list_group_stats_mean(
+            nat.ptr(stats.contiguous()), nat.ptr(flags.contiguous()), n, m, nat.ptr(exposure),
+            nat.ptr(present.contiguous() if present is not None and n_groups else None), n_groups, nat.ptr(mean),
+            nat.ptr(cov), nat.ptr(n_eval), nat.stream_handle(self.device)), "dcue_list_group_stats_mean")
+        return mean, cov, n_eval
 
 
 def check_reasons(reasons):
@@ -591,7 +848,7 @@ class TopKMetrics(_Workspace):
         return mean, cov, n_eval
 
     def evaluate(self, query_feat, cand_feat, queries, ks, query_batch=None, per_query=False, diversity=None,
-                 pool=None, rel=None, ild=False):
+                 pool=None, rel=None, ild=False, group_of=None, max_per_group=None, cap_rounds=4, group_stats=False):
         """{"ks", "n_evaluated", "precision", "recall", "ndcg", "map", "mrr", "hit", "coverage"}: each
         metric a float64 array over the cutoffs, the mean over the queries with a non-empty truth row;
         per_query adds "per_query" (numpy [n, m, 6], slots in nat.TOPK_METRIC_NAMES order) and "flags".
@@ -603,15 +860,31 @@ class TopKMetrics(_Workspace):
         of the lists that were scored, over those with at least two entries at every cutoff) and
         "n_ild" (their number), by dcue_list_ild / dcue_list_ild_mean on the same device lists.
 
+        group_of / max_per_group / cap_rounds: the lists are TopK.topk_raw's capped ones. group_stats (with
+        group_of) adds "group_distinct" and "group_top" (float64 over the cutoffs: the mean number of
+        distinct groups in a list's first K entries, and of the most entries one group holds),
+        "group_coverage" (the share of the groups that have a candidate which appear in some list's first
+        K entries) and "n_group" (the lists behind them), by dcue_list_group_stats /
+        dcue_list_group_stats_mean on the same device lists.
+
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite, as TopK.topk does."""
         ks, cut = self._cutoffs(ks)
         queries = np.asarray(queries, dtype=np.int64).reshape(-1)
         n, m, k = len(queries), len(ks), ks[-1]
-        if diversity is not None:
+        if diversity is not None or max_per_group is not None:
             check_pool(k, pool)
         elif pool is not None or rel is not None:
-            raise ValueError("pool and rel belong to diversity=, which is not set")
+            raise ValueError("pool and rel belong to diversity= (pool also to max_per_group=), which is not set")
+        cap_kw = {}
+        if max_per_group is not None:
+            cap_kw = dict(group_of=group_of, max_per_group=max_per_group, cap_rounds=cap_rounds)
+        if group_stats:
+            g_dev, n_groups, _ = self.topk._group_args(group_of, 1, 1)
+            gc = self.topk._cap()
+            g_out = torch.zeros((max(n, 1), m, nat.GROUP_N_STATS), dtype=torch.int32, device=self.device)
+            g_flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+            g_exposure = gc.new_exposure(m, n_groups)
         if self.topk.excl_ptr is None and query_feat.shape[0] != self.n_query_rows:
             raise ValueError("query factors have %d rows, the truth CSR %d" % (query_feat.shape[0], self.n_query_rows))
         qb = int(self.topk.DEFAULT_QUERY_BATCH if query_batch is None else query_batch)
@@ -627,17 +900,20 @@ class TopKMetrics(_Workspace):
             ild_flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         for q0 in range(0, n, qb):
             part = queries[q0:q0 + qb]
-            if diversity is None:
+            if diversity is None and not cap_kw:
                 idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb)
             else:
                 idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb,
-                                                           diversity=diversity, pool=pool, rel=rel)
+                                                           diversity=diversity, pool=pool, rel=rel, **cap_kw)
             q = torch.as_tensor(part.astype(np.int32)).to(self.device)
             self._metrics_into(idx, count, q, cut, m, out[q0:], flags[q0:], exposure)
             nonfinite[q0:q0 + len(part)] = tflags
             if ild:
                 lists = div._device_lists(idx, count, cand_feat)
                 div._ild_into(*lists[:3], ks, cut, ild_out[q0:], ild_flags[q0:])
+            if group_stats:
+                gc._stats_into(idx.contiguous(), count.contiguous(), g_dev, n_groups, ks, cut, g_out[q0:],
+                               g_flags[q0:], g_exposure)
         bad = (nonfinite[:n].cpu().numpy() & 2).astype(bool)
         if bad.any():
             raise self.topk._nonfinite(queries, bad)
@@ -651,6 +927,15 @@ class TopKMetrics(_Workspace):
             ild_mean, n_ild = div.ild_mean_raw(ild_out[:n], ild_flags[:n])
             res["ild"] = ild_mean.cpu().numpy()
             res["n_ild"] = int(n_ild.cpu().numpy()[0])
+        if group_stats:
+            check_group_flags(queries, g_flags[:n])
+            present = torch.zeros(max(n_groups, 1), dtype=torch.uint8, device=self.device)[:n_groups]
+            members = g_dev if self.cand_mask is None else g_dev[self.cand_mask != 0]
+            present[members[members >= 0].long()] = 1
+            g_mean, g_cov, n_g = gc.mean_raw(g_out[:n], g_flags[:n], g_exposure, present)
+            g_mean = g_mean.cpu().numpy()
+            res.update(group_distinct=g_mean[:, 0].copy(), group_top=g_mean[:, 1].copy(),
+                       group_coverage=g_cov.cpu().numpy(), n_group=int(n_g.cpu().numpy()[0]))
         if per_query:
             res["per_query"] = out[:n].cpu().numpy()
             res["flags"] = flags[:n].cpu().numpy()

@@ -1218,6 +1218,73 @@ int dcue_augment_params_host(const dcue_crop_config* cfg, const dcue_augment_con
                              const int64_t* lengths_host, const int64_t* track_ids_host, int64_t n,
                              float* gain_host, int32_t* freq_pw_host, int32_t* time_pw_host);
 
+/* ------------------------------ group-aware serving: per-group caps, group statistics (added under ABI 17) */
+/* "At most two songs per artist": a cap on how many entries of one group a served list may hold, and the
+ * group-level statistics of such lists, on the lists dcue_topk / dcue_topk_scored / dcue_list_mmr leave on
+ * the device. A group is whatever the caller's item -> group map says: artist, album, label. The
+ * reference has no counterpart.
+ * Pool. idx [n_lists][pool] / score [n_lists][pool] / count [n_lists]: those calls' out_idx / out_score /
+ *   out_count at k = pool, 1 <= pool <= DCUE_TOPK_MAX_K; c = count clamped to 0..pool. Entries at j >= c
+ *   are never read. Pool POSITIONS are the entities, as in dcue_list_mmr: an index named twice is two
+ *   entries.
+ * Groups. group_of int32 [n_cand] (device): a value in [0, n_groups) is the candidate's group; -1 means
+ *   ungrouped -- never capped, and it counts against nothing; any other value sets
+ *   DCUE_GROUP_FLAG_BAD_GROUP for the list.
+ * Carry (carry_idx, carry_score, carry_count: all null or all given). carry_idx / carry_score
+ *   [n_lists][k_out], carry_count [n_lists] clamped to 0..k_out: entries an earlier call already kept for
+ *   the list. They go to the output first, unchanged, and count toward their groups. The carry arrays
+ *   must not overlap the outputs.
+ * Rule. For pool position j < c with group g >= 0, r_j = (carried entries of group g) + (positions i < j
+ *   of group g); the position survives iff g < 0 or r_j < cap. The output is the carry followed by the
+ *   surviving positions in pool order, truncated to k_out entries, 1 <= k_out <= DCUE_TOPK_MAX_K. r_j
+ *   depends on earlier positions' groups, not on earlier decisions, so this equals the sequential greedy
+ *   walk that keeps an entry while its group holds fewer than cap kept ones.
+ * Outputs. out_idx / out_score [n_lists][k_out]: idx and score bits copied, never recomputed; the tail is
+ *   -1 / -inf as dcue_topk pads. out_count [n_lists]: the real entries. out_dropped [n_lists] (nullable):
+ *   the pool positions the cap removed before the list filled (the walk stops at k_out entries).
+ * Flags. out_flags[i] bit 1 (DCUE_LIST_FLAG_BAD_INDEX): a pool entry j < c or a carried entry lies
+ *   outside [0, n_cand) -- each is range-checked before it addresses anything; bit 4
+ *   (DCUE_GROUP_FLAG_BAD_GROUP): an in-range entry's group is below -1 or at least n_groups. A list with
+ *   either gets count 0, dropped 0 and all padding. Bit 3 (DCUE_GROUP_FLAG_SHORT): out_count < k_out --
+ *   the pool ran out under the cap; the entries are valid.
+ * Statistics. For a list idx [n_lists][k] / count and a cutoff K, n_K = min(K, c): distinct@K = the
+ *   distinct groups among the first n_K positions, every ungrouped position counting as one of its own;
+ *   top@K = the most positions one group holds (1 if all are ungrouped and n_K > 0, 0 if n_K = 0).
+ *   out_stats int32 [n_lists][n_cutoffs][2] = (distinct, top). Flags: bits 1 and 4 as above; a flagged
+ *   list's values are 0 and it adds no exposure. group_exposure (nullable) int32 [n_cutoffs][n_groups]:
+ *   position j < c of an unflagged list with group g >= 0 adds 1 to group_exposure[i][g], i the first
+ *   cutoff with j < k_i (integer atomics; the kernel accumulates, the caller zeroes).
+ *   cutoffs_host[n_cutoffs] (HOST memory): 1 <= k_1 < ... < k_m <= k, 1 <= m <= 8.
+ * dcue_list_group_stats_mean: out_mean [n_cutoffs][2] = double(int64 column sum over the lists with flags
+ *   == 0) / double(their number), *out_n_evaluated their number (means 0 where it is 0): an exact integer
+ *   sum and one division, so the means are the same bits however `stats` was filled. With group_exposure,
+ *   out_coverage[i] = (groups with a non-zero exposure in cutoffs 0..i) / (groups with a non-zero byte in
+ *   group_present uint8 [n_groups]; n_groups with a null mask), 0 where the denominator is 0;
+ *   out_coverage is null exactly when group_exposure is.
+ * Invariance. A list's outputs are a function of that list, its carry and the groups they name.
+ * One launch per call, no workspace, no floating-point arithmetic on the lists; asynchronous on `stream`.
+ * Every argument is validated on the host before the first device call, each refusal with a
+ * dcue_last_error text (DCUE_ERR_INVALID: a null required pointer, pool / k / k_out outside
+ * 1..DCUE_TOPK_MAX_K, cap < 1, n_groups < 0, n_cand <= 0, n_lists < 0, carry arrays partly given, bad
+ * cutoffs, group_exposure without out_coverage or the reverse; DCUE_ERR_UNSUPPORTED: n_cand beyond
+ * dcue_topk's bound). n_lists == 0 is DCUE_OK (the mean call then writes zeros). */
+#define DCUE_GROUP_FLAG_SHORT 8
+#define DCUE_GROUP_FLAG_BAD_GROUP 16
+#define DCUE_GROUP_N_STATS 2 /* distinct, top */
+int dcue_list_group_cap(const int32_t* idx, const float* score, const int32_t* count, int32_t n_lists, int32_t pool,
+                        const int32_t* group_of, int64_t n_cand, int32_t n_groups, int32_t cap, int32_t k_out,
+                        const int32_t* carry_idx, const float* carry_score, const int32_t* carry_count,
+                        int32_t* out_idx, float* out_score, int32_t* out_count, int32_t* out_dropped,
+                        int32_t* out_flags, void* stream);
+int dcue_list_group_stats(const int32_t* idx, const int32_t* count, int32_t n_lists, int32_t k,
+                          const int32_t* group_of, int64_t n_cand, int32_t n_groups, const int32_t* cutoffs_host,
+                          int32_t n_cutoffs, int32_t* out_stats /* [n][m][2] */, int32_t* out_flags,
+                          int32_t* group_exposure, void* stream);
+int dcue_list_group_stats_mean(const int32_t* stats, const int32_t* flags, int32_t n_lists, int32_t n_cutoffs,
+                               const int32_t* group_exposure, const uint8_t* group_present, int32_t n_groups,
+                               double* out_mean /* [m][2] */, double* out_coverage, int32_t* out_n_evaluated,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

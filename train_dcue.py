@@ -14,6 +14,11 @@ this is that driver for the MI355X build:
                                                   # MMR re-ranked lists (--recommend-pool: the pool)
   python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-reasons 3 --reasons-out why.csv
                                                   # + each pick's 3 nearest songs of the user's history
+  python train_dcue.py ... --artists artists.csv --recommend-k 10 --recommend-out recs.csv --recommend-max-per-artist 2
+                                                  # at most two songs per artist (--recommend-new-artists:
+                                                  # none by an artist the user has played)
+  python train_dcue.py ... --artists artists.csv --recommend-k 10 --recommend-out recs.csv --recommend-artists-out a.csv
+                                                  # + each user's 10 best artists
   python train_dcue.py ... --eval-k 10,50 --eval-out metrics.json --eval-ild --eval-diversity 0.7
                                                   # + intra-list diversity, of the MMR re-ranked lists
 
@@ -77,6 +82,20 @@ def parse(argv=None):
                          "it by the item factors' cosine (DCUE.explain / explain_for), written to --reasons-out")
     ap.add_argument("--reasons-out", help="CSV for --recommend-reasons: user_id, rank, song_id, reason_rank, "
                                           "reason_song_id, similarity")
+    ap.add_argument("--artists", metavar="FILE.csv",
+                    help="columns song_id,artist: who recorded each song (DCUE.set_artists); songs it leaves out "
+                         "have no artist and are never capped")
+    ap.add_argument("--recommend-max-per-artist", type=int, metavar="M",
+                    help="with --artists: no artist holds more than M songs of a --recommend-k / --recommend-for "
+                         "list (DCUE.recommend(max_per_artist=M)); --recommend-pool sets the pool here too")
+    ap.add_argument("--recommend-new-artists", action="store_true",
+                    help="with --artists: the lists leave out every song by an artist the user has played")
+    ap.add_argument("--recommend-artists-out", metavar="FILE.csv",
+                    help="with --artists and --recommend-k: each training user's K best artists "
+                         "(DCUE.recommend_artists): user_id, rank, artist, song_id, score")
+    ap.add_argument("--eval-artists", action="store_true",
+                    help="with --artists: --eval-k also reports artists@K, artist_top@K and artist_coverage@K, and "
+                         "scores the --recommend-max-per-artist lists when that is set")
     ap.add_argument("--eval-k", metavar="K[,K...]",
                     help="after training, Precision / Recall / NDCG / MAP / MRR / HitRate / coverage at these "
                          "cutoffs over the val and the test split (DCUE.evaluate_topk)")
@@ -139,8 +158,23 @@ def parse(argv=None):
         ap.error("--recommend-for needs --recommend-k and --recommend-out")
     if (args.recommend_diversity is not None or args.recommend_pool is not None) and args.recommend_k <= 0:
         ap.error("--recommend-diversity / --recommend-pool need --recommend-k")
-    if args.recommend_pool is not None and args.recommend_diversity is None:
+    if (args.recommend_pool is not None and args.recommend_diversity is None
+            and args.recommend_max_per_artist is None):
         ap.error("--recommend-pool needs --recommend-diversity")
+    artist_flags = [("--recommend-max-per-artist", args.recommend_max_per_artist is not None),
+                    ("--recommend-new-artists", args.recommend_new_artists),
+                    ("--recommend-artists-out", bool(args.recommend_artists_out)), ("--eval-artists", args.eval_artists)]
+    for flag, given in artist_flags:
+        if given and not args.artists:
+            ap.error("%s needs --artists" % flag)
+    if any(given for _, given in artist_flags[:3]) and args.recommend_k <= 0:
+        ap.error("--recommend-max-per-artist / --recommend-new-artists / --recommend-artists-out need --recommend-k")
+    if args.recommend_max_per_artist is not None and args.recommend_max_per_artist < 1:
+        ap.error("--recommend-max-per-artist must be at least 1, got %r" % args.recommend_max_per_artist)
+    if args.recommend_artists_out and args.recommend_for:
+        ap.error("--recommend-artists-out goes without --recommend-for")
+    if args.eval_artists and not args.eval_k:
+        ap.error("--eval-artists needs --eval-k")
     if (args.recommend_reasons is not None) != bool(args.reasons_out):
         ap.error("--recommend-reasons and --reasons-out go together")
     if args.recommend_reasons is not None and args.recommend_k <= 0:
@@ -229,6 +263,11 @@ def main(argv=None):
                 neg_hard=args.neg_hard, augment=augment_of(args))
     dcue.fit(train, val, test, pred, truth, items, len(train.user_index), len(train.item_index),
              triplets_path, metadata_path, args.save_dir)
+    artist_kw = {}
+    if args.artists:
+        names = pd.read_csv(args.artists, dtype=str)
+        dcue.set_artists(dict(zip(names["song_id"], names["artist"])))
+        artist_kw = dict(max_per_artist=args.recommend_max_per_artist, new_artists=args.recommend_new_artists)
     if args.recommend_k > 0 and args.recommend_out:
         if args.recommend_for:
             new = pd.read_csv(args.recommend_for, dtype=str)
@@ -236,51 +275,72 @@ def main(argv=None):
             write_recommendations(dcue, list(histories), args.recommend_k, args.recommend_out,
                                   histories=histories, seed=args.seed, diversity=args.recommend_diversity,
                                   pool=args.recommend_pool, reasons=args.recommend_reasons,
-                                  reasons_path=args.reasons_out)
+                                  reasons_path=args.reasons_out, **artist_kw)
         else:
             write_recommendations(dcue, list(train.uniq_users), args.recommend_k, args.recommend_out,
                                   diversity=args.recommend_diversity, pool=args.recommend_pool,
-                                  reasons=args.recommend_reasons, reasons_path=args.reasons_out)
+                                  reasons=args.recommend_reasons, reasons_path=args.reasons_out, **artist_kw)
+        if args.recommend_artists_out:
+            write_artists(dcue, list(train.uniq_users), args.recommend_k, args.recommend_artists_out,
+                          new_artists=args.recommend_new_artists)
     if args.eval_k:
-        write_metrics(dcue, val, test, args.eval_k, args.eval_out, diversity=args.eval_diversity, ild=args.eval_ild)
+        write_metrics(dcue, val, test, args.eval_k, args.eval_out, diversity=args.eval_diversity, ild=args.eval_ild,
+                      artists=args.eval_artists, max_per_artist=args.recommend_max_per_artist if args.eval_artists else None)
     return dcue
 
 
-def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False):
-    """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs
-    (diversity: of the MMR re-ranked lists; ild: with their intra-list diversity)."""
+def write_artists(dcue, users, k, path, new_artists=False):
+    """The best-by-validation factors' k best artists per user (DCUE.recommend_artists), one CSV row per
+    (user, rank): the artist, and the song of theirs that ranks highest for the user with its score."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
-    res = {"val": dcue.evaluate_topk(val, ks=ks, diversity=diversity, ild=ild),
-           "test": dcue.evaluate_topk(test, ks=ks, diversity=diversity, ild=ild)}
+    lists = dcue.recommend_artists(users, k=k, new_artists=new_artists)
+    rows = [(u, r + 1, artist, song, score) for u, lst in zip(users, lists) for r, (artist, song, score) in enumerate(lst)]
+    pd.DataFrame(rows, columns=["user_id", "rank", "artist", "song_id", "score"]).to_csv(path, index=False)
+
+
+def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False, artists=False, max_per_artist=None):
+    """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs
+    (diversity: of the MMR re-ranked lists; ild: with their intra-list diversity; artists: with the
+    artist numbers; max_per_artist: of the capped lists)."""
+    if dcue.best_user_factors is not None:
+        dcue.insert_best_factors()
+    kw = dict(artists=True, max_per_artist=max_per_artist) if artists else {}
+    res = {"val": dcue.evaluate_topk(val, ks=ks, diversity=diversity, ild=ild, **kw),
+           "test": dcue.evaluate_topk(test, ks=ks, diversity=diversity, ild=ild, **kw)}
     with open(path, "w") as f:
         json.dump(res, f, indent=1, sort_keys=True)
         f.write("\n")
 
 
 def write_recommendations(dcue, users, k, path, histories=None, seed=0, diversity=None, pool=None, reasons=None,
-                          reasons_path=None):
+                          reasons_path=None, max_per_artist=None, new_artists=False):
     """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank).
     histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for).
     diversity / pool: MMR re-ranked lists (DCUE.recommend). reasons / reasons_path: also each pick's
-    `reasons` nearest history songs (DCUE.explain / explain_for), one row per (user, rank, reason_rank)."""
+    `reasons` nearest history songs (DCUE.explain / explain_for), one row per (user, rank, reason_rank).
+    max_per_artist / new_artists: as DCUE.recommend (none without artists: today's calls)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
+    akw = {}
+    if max_per_artist is not None or new_artists:
+        akw = dict(max_per_artist=max_per_artist, new_artists=new_artists)
     if reasons is not None:
         if histories is not None:
             lists = dcue.explain_for([histories[u] for u in users], k=k, reasons=reasons, seed=seed,
-                                     diversity=diversity, pool=pool)
+                                     diversity=diversity, pool=pool, **akw)
         else:
-            lists = dcue.explain(users, k=k, reasons=reasons, diversity=diversity, pool=pool)
+            lists = dcue.explain(users, k=k, reasons=reasons, diversity=diversity, pool=pool, **akw)
         why = [(u, r + 1, song, j + 1, h, sim) for u, lst in zip(users, lists)
                for r, (song, _, because) in enumerate(lst) for j, (h, sim) in enumerate(because)]
         pd.DataFrame(why, columns=["user_id", "rank", "song_id", "reason_rank", "reason_song_id",
                                    "similarity"]).to_csv(reasons_path, index=False)
         lists = [[(song, score) for song, score, _ in lst] for lst in lists]
     elif histories is not None:
-        lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed, diversity=diversity, pool=pool)
+        lists = dcue.recommend_for([histories[u] for u in users], k=k, seed=seed, diversity=diversity, pool=pool,
+                                   **akw)
     else:
-        lists = dcue.recommend(users, k=k, diversity=diversity, pool=pool)
+        lists = dcue.recommend(users, k=k, diversity=diversity, pool=pool, **akw)
     rows = [(u, r + 1, song, score) for u, lst in zip(users, lists) for r, (song, score) in enumerate(lst)]
     pd.DataFrame(rows, columns=["user_id", "rank", "song_id", "score"]).to_csv(path, index=False)
 
