@@ -52,6 +52,7 @@ struct TopkArgs {
   int S;
   unsigned long long* parts;  // [nq][S][k]
   int32_t* pflags;            // [nq][S]
+  const float* prior;         // [nc] added to every score of the candidate (dcue_topk_prior), or null
 };
 
 __host__ __device__ constexpr size_t topk_lds_bytes(int dp, int kp, int qt) {
@@ -172,7 +173,10 @@ __device__ __forceinline__ bool topk_eligible(const TopkArgs& a, const TopkLds& 
 // The MFMA loop restates k_rank_scores' (rank.hip) and must stay in step with it: recommend-versus-score
 // parity rests on the two loops' k order. A shared forceinline loop was tried; it changed how the
 // compiler keeps the accumulators in both kernels, and top-K ran 1 % to 5 % slower by the variant.
-template <int MT>
+// PRIOR (dcue_topk_prior): s = fl32(s0 + prior[c]), one addition on the final accumulator, -0 folded
+// again; the lane's prior is prefetched with its mask byte. The PRIOR = false instances are the plain
+// calls' and hold none of it.
+template <int MT, bool PRIOR>
 __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
   constexpr int QT = 16 * MT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -208,6 +212,7 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
   }
   float4 pre[16];
   int mcur = 0, mnext = 0;  // this lane's candidate's mask byte, current and prefetched tile
+  float pcur = 0.f, pnext = 0.f;  // (PRIOR) and its prior
   if (t_begin < t_end) {
     const float* src = a.cn + (size_t)t_begin * 64 * dp;
 #pragma unroll
@@ -215,6 +220,7 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
       if (i < u) pre[i] = ld4(src + 4 * (tid + 256 * i));
     const int c = t_begin * 64 + 16 * w + l16;
     mcur = c < a.nc ? (a.mask ? a.mask[c] : 1) : 0;
+    if constexpr (PRIOR) pcur = c < a.nc ? a.prior[c] : 0.f;
   }
   for (int e = tid; e < QT * dp4; e += 256) {
     const int r = e / dp4, k4 = e - r * dp4;
@@ -250,6 +256,7 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
         if (i < u) pre[i] = ld4(src + 4 * (tid + 256 * i));
       const int cn1 = (t + 1) * 64 + 16 * w + l16;
       mnext = cn1 < a.nc ? (a.mask ? a.mask[cn1] : 1) : 0;
+      if constexpr (PRIOR) pnext = cn1 < a.nc ? a.prior[cn1] : 0.f;
     }
     f32x4 acc[MT];
 #pragma unroll
@@ -274,6 +281,8 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
     float mag = 0.f;  // finite unless one of the lane's scores is NaN / inf
 #pragma unroll
     for (int m = 0; m < MT; ++m) mag += (fabsf(acc[m][0]) + fabsf(acc[m][1])) + (fabsf(acc[m][2]) + fabsf(acc[m][3]));
+    // (PRIOR) |s0| + |p| >= |s0 + p| and rounding is monotone: a NaN / inf sum makes mag NaN / inf
+    if constexpr (PRIOR) mag += fabsf(pcur);
     const bool odd = !(mag < __builtin_inff());
     if (c < a.nc && (mcur || odd)) {
 #pragma unroll
@@ -282,7 +291,8 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
         const float tfr[4] = {tf.x, tf.y, tf.z, tf.w};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float s = acc[m][r] + 0.f;  // -0 -> +0: one key per value
+          float s = acc[m][r] + 0.f;  // -0 -> +0: one key per value
+          if constexpr (PRIOR) s = (s + pcur) + 0.f;
           if (odd && !(fabsf(s) < __builtin_inff())) {  // NaN / inf: flagged where the candidate is eligible
             const int ql = 16 * m + 4 * g + r;
             if (q0 + ql < a.nq && topk_eligible(a, L, c, ql)) {
@@ -296,6 +306,8 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
       }
     }
     mcur = mnext;
+    const float padd = pcur;  // (PRIOR) the pending scores' prior: this tile's
+    if constexpr (PRIOR) pcur = pnext;
     for (;;) {
       for (unsigned p = pend; p;) {
         const int b = __ffs(p) - 1;
@@ -306,6 +318,7 @@ __global__ __launch_bounds__(256) void k_topk_scores(TopkArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             if (b == 4 * m + r) s = acc[m][r] + 0.f;
+        if constexpr (PRIOR) s = (s + padd) + 0.f;
         const int ql = 16 * (b >> 2) + 4 * g + (b & 3);
         const unsigned long long key = ((unsigned long long)ord_key(s) << 32) | low;
         if (key > L.thr[ql]) {
@@ -398,32 +411,12 @@ static int topk_check(int64_t n_cand, int32_t d, int32_t query_batch, int32_t k,
   return DCUE_OK;
 }
 
-}  // namespace dcue
-
-using namespace dcue;
-
-extern "C" {
-
-int dcue_topk_workspace_bytes(int64_t n_cand, int32_t d, int32_t query_batch, int32_t k, int32_t cand_split,
-                              size_t* bytes) {
-  if (!bytes) return DCUE_ERR_INVALID;
-  TRY(topk_check(n_cand, d, query_batch, k, cand_split));
-  // auto: the split follows the number of queries of a pass (at most query_batch); q * split(q) is
-  // below 64 * kTopkFillWgs + q + 64 and below 32 q
-  const size_t qb = (size_t)query_batch;
-  const size_t bound = (size_t)64 * kTopkFillWgs + qb + 64;
-  const size_t rows = cand_split > 0 ? qb * (size_t)(cand_split < kTopkMaxSplit ? cand_split : kTopkMaxSplit)
-                                     : (qb * kTopkMaxSplit < bound ? qb * kTopkMaxSplit : bound);
-  TopkWs w;
-  *bytes = topk_carve(n_cand, d, query_batch, k, rows, nullptr, &w);
-  return DCUE_OK;
-}
-
-int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
-                     int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
-                     const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k, int32_t query_batch,
-                     int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
-                     int32_t* out_count, int32_t* out_flags, void* stream) {
+// dcue_topk_scored (cand_prior null) and dcue_topk_prior
+static int topk_run(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                    int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
+                    const int32_t* excl_idx, const uint8_t* cand_mask, const float* cand_prior, int32_t k,
+                    int32_t query_batch, int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx,
+                    float* out_score, int32_t* out_count, int32_t* out_flags, void* stream) {
   if (score != DCUE_SCORE_COSINE && score != DCUE_SCORE_DOT) return DCUE_ERR_INVALID;
   // the prep pass of both sides: unit rows (cosine) or the raw rows (inner product), zero-padded to dp
   const auto prep = score == DCUE_SCORE_DOT ? launch_rank_pad : launch_rank_normalize;
@@ -447,11 +440,19 @@ int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_row
   hipStream_t s = (hipStream_t)stream;
   static bool attr = false;
   if (!attr) {
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        kTopkLdsBudget));
-    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        kTopkLdsBudget));
     attr = true;
+  }
+  static bool attr_prior = false;
+  if (cand_prior && !attr_prior) {
+    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<4, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kTopkLdsBudget));
+    DCUE_HIP_CHECK(hipFuncSetAttribute((const void*)k_topk_scores<2, true>,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, kTopkLdsBudget));
+    attr_prior = true;
   }
   const size_t lds = topk_lds_bytes(dp, 1 << lkp, qt);
   // zero rows past the last candidate / query of a tile: the kernels load whole tiles
@@ -480,11 +481,18 @@ int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_row
     a.S = S;
     a.parts = w.parts;
     a.pflags = w.pflags;
+    a.prior = cand_prior;
     const dim3 grid((unsigned)((nq + qt - 1) / qt), (unsigned)S);
-    if (qt == 64)
-      DCUE_LAUNCH(k_topk_scores<4>, grid, dim3(256), lds, s, a);
-    else
-      DCUE_LAUNCH(k_topk_scores<2>, grid, dim3(256), lds, s, a);
+    if (cand_prior) {
+      if (qt == 64)
+        DCUE_LAUNCH((k_topk_scores<4, true>), grid, dim3(256), lds, s, a);
+      else
+        DCUE_LAUNCH((k_topk_scores<2, true>), grid, dim3(256), lds, s, a);
+    } else if (qt == 64) {
+      DCUE_LAUNCH((k_topk_scores<4, false>), grid, dim3(256), lds, s, a);
+    } else {
+      DCUE_LAUNCH((k_topk_scores<2, false>), grid, dim3(256), lds, s, a);
+    }
     DCUE_LAUNCH_CHECK();
     DCUE_LAUNCH(k_topk_merge, dim3((unsigned)nq), dim3(256), 0, s, (const unsigned long long*)w.parts,
                 (const int32_t*)w.pflags, S, (int)k, (int)q0, out_idx, out_score, out_count, out_flags);
@@ -492,6 +500,56 @@ int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_row
   }
   DCUE_HIP_CHECK(hipStreamSynchronize(s));
   return DCUE_OK;
+}
+
+}  // namespace dcue
+
+using namespace dcue;
+
+extern "C" {
+
+int dcue_topk_workspace_bytes(int64_t n_cand, int32_t d, int32_t query_batch, int32_t k, int32_t cand_split,
+                              size_t* bytes) {
+  if (!bytes) return DCUE_ERR_INVALID;
+  TRY(topk_check(n_cand, d, query_batch, k, cand_split));
+  // auto: the split follows the number of queries of a pass (at most query_batch); q * split(q) is
+  // below 64 * kTopkFillWgs + q + 64 and below 32 q
+  const size_t qb = (size_t)query_batch;
+  const size_t bound = (size_t)64 * kTopkFillWgs + qb + 64;
+  const size_t rows = cand_split > 0 ? qb * (size_t)(cand_split < kTopkMaxSplit ? cand_split : kTopkMaxSplit)
+                                     : (qb * kTopkMaxSplit < bound ? qb * kTopkMaxSplit : bound);
+  TopkWs w;
+  *bytes = topk_carve(n_cand, d, query_batch, k, rows, nullptr, &w);
+  return DCUE_OK;
+}
+
+int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                     int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
+                     const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k, int32_t query_batch,
+                     int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx, float* out_score,
+                     int32_t* out_count, int32_t* out_flags, void* stream) {
+  return topk_run(score, query_feat, n_query_rows, cand_feat, n_cand, d, queries, n_queries, excl_ptr, excl_idx,
+                  cand_mask, nullptr, k, query_batch, cand_split, ws, ws_bytes, out_idx, out_score, out_count,
+                  out_flags, stream);
+}
+
+int dcue_topk_prior(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                    int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries, const int64_t* excl_ptr,
+                    const int32_t* excl_idx, const uint8_t* cand_mask, const float* cand_prior, int32_t k,
+                    int32_t query_batch, int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx,
+                    float* out_score, int32_t* out_count, int32_t* out_flags, void* stream) {
+  const int st = topk_run(score, query_feat, n_query_rows, cand_feat, n_cand, d, queries, n_queries, excl_ptr,
+                          excl_idx, cand_mask, cand_prior, k, query_batch, cand_split, ws, ws_bytes, out_idx,
+                          out_score, out_count, out_flags, stream);
+  // (the refusals are host checks made before the first device call; a HIP failure keeps its own text)
+  if (st == DCUE_ERR_INVALID)
+    set_last_message("dcue_topk_prior: a null required pointer, an unknown score, excl_ptr without excl_idx or the "
+                     "reverse, or k / n_cand / d / query_batch / cand_split / a count out of range");
+  else if (st == DCUE_ERR_UNSUPPORTED)
+    set_last_message("dcue_topk_prior: d above 256 or n_cand beyond dcue_topk's bound");
+  else if (st == DCUE_ERR_WORKSPACE)
+    set_last_message("dcue_topk_prior: the workspace is smaller than dcue_topk_workspace_bytes says");
+  return st;
 }
 
 int dcue_topk(const float* query_feat, int64_t n_query_rows, const float* cand_feat, int64_t n_cand, int32_t d,

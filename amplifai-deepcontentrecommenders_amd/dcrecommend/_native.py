@@ -192,6 +192,10 @@ EXPLAIN_FLAG_NO_HISTORY = 1
 # LIST_FLAG_BAD_INDEX)
 GROUP_FLAG_SHORT, GROUP_FLAG_BAD_GROUP = 8, 16
 GROUP_N_STATS = 2  # distinct, top
+# dcue_list_item_stats / dcue_exposure_gini (added under ABI 17): DCUE_ITEM_FLAG_EMPTY, DCUE_ITEM_N_STATS (bit 1:
+# LIST_FLAG_BAD_INDEX)
+ITEM_FLAG_EMPTY = 1
+ITEM_N_STATS = 2  # value (novelty), tail
 # dcue_debug_delay sites (include/dcue.h)
 DEBUG_SITES = ("user_fwd", "user_bwd", "wgrad_hi", "wgrad_2", "fc_wgrad", "late_adam", "prologue", "lookahead",
                "conv2", "dgrad_2", "wgrad_1", "text_fwd", "dgrad_4", "dgrad_3")
@@ -283,6 +287,9 @@ _SIGS = {
     "dcue_topk_scored": ([ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
                           _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P,
                           _P, _P], ctypes.c_int),
+    "dcue_topk_prior": ([ctypes.c_int32, _P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_int32,
+                         _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P,
+                         _P, _P, _P], ctypes.c_int),
     "dcue_wrmf_objective_workspace_bytes": ([ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                              ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
     "dcue_wrmf_objective": ([_P, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int32, _P, _P, _P, ctypes.c_double,
@@ -308,6 +315,12 @@ _SIGS = {
                                ctypes.c_int32, _P, _P, _P, _P], ctypes.c_int),
     "dcue_list_group_stats_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P, _P, _P],
                                    ctypes.c_int),
+    "dcue_list_item_stats": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int64, _P, ctypes.c_int32, _P,
+                              _P, _P], ctypes.c_int),
+    "dcue_list_item_stats_mean": ([_P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P], ctypes.c_int),
+    "dcue_exposure_gini_workspace_bytes": ([ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
+    "dcue_exposure_gini": ([_P, _P, ctypes.c_int64, ctypes.c_int32, _P, ctypes.c_size_t, _P, _P, _P], ctypes.c_int),
     "dcue_factor_repeat_mean": ([_P, ctypes.c_int64, ctypes.c_int32, _P], ctypes.c_int),
     "dcue_foldin_workspace_bytes": ([ctypes.POINTER(Dims), ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
                                      ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)], ctypes.c_int),
@@ -380,8 +393,10 @@ def lib():
 def check(status, what):
     if status != 0:
         msg = "%s failed: %s" % (what, STATUS.get(status, status))
+        # the calls that leave a dcue_last_error text
         if status == 3 or what.startswith(("dcue_logmel", "dcue_crop", "dcue_augment", "dcue_resample",
-                                         "dcue_list_group")):  # the calls that leave a dcue_last_error text
+                                         "dcue_list_group", "dcue_topk_prior", "dcue_list_item",
+                                         "dcue_exposure_gini")):
             msg += " [%s]" % lib().dcue_last_error().decode(errors="replace")
         raise RuntimeError(msg)
 

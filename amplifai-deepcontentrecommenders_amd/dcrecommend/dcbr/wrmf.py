@@ -207,7 +207,7 @@ class WRMF:
         return self._serve[key]
 
     def recommend(self, users, k=10, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
-                  pool=None, groups=None, max_per_group=None):
+                  pool=None, groups=None, max_per_group=None, item_prior=None):
         """The k best items for each user row by x_u . y_i: (idx int64 [n, k], score float32 [n, k],
         count int32 [n]) numpy arrays, best first, short lists padded with -1 / -inf. exclude_seen
         drops the items of the user's by_user row. item_factors [n_cand, factors] (device) replaces
@@ -223,13 +223,18 @@ class WRMF:
         max_per_group with groups, an int array by candidate row (an item's artist, album, ...; -1: none):
         no group holds more than that many items of a list (rank.TopK.topk_raw max_per_group=:
         dcue_list_group_cap on the `pool` best items, short lists ranked deeper; with diversity= the
-        pool is capped before MMR picks from it)."""
+        pool is capped before MMR picks from it).
+
+        item_prior (None: the plain inner product): a finite float array by candidate row added to every
+        score of its item inside the fused ranking (dcue_topk_prior) -- item biases, a popularity
+        correction, boosts; the scores returned are the sums, and the prior reaches every ranking the call
+        makes (the pool of diversity=, each round of max_per_group=)."""
         cand = self._candidates(item_factors)
         if exclude_seen and cand.shape[0] != self.item_factors.shape[0]:
             raise ValueError("exclude_seen needs a candidate table with the fit's %d items" % self.item_factors.shape[0])
         tk = self._topk(exclude_seen, cand_mask, int(cand.shape[0]))
         return tk.topk(self.user_factors, cand, np.asarray(users, dtype=np.int64).reshape(-1), k,
-                       diversity=diversity, pool=pool, **self._group_kw(groups, max_per_group))
+                       diversity=diversity, pool=pool, prior=item_prior, **self._group_kw(groups, max_per_group))
 
     @staticmethod
     def _group_kw(groups, max_per_group):
@@ -241,20 +246,21 @@ class WRMF:
         return dict(group_of=groups, max_per_group=max_per_group)
 
     def explain(self, users, k=10, reasons=3, exclude_seen=True, item_factors=None, cand_mask=None, diversity=None,
-                pool=None):
+                pool=None, item_prior=None):
         """recommend()'s lists with the reason for every pick: (idx, score, count) as recommend() returns
         them (the same dcue_topk_scored call) plus why_idx int64 [n, k, reasons] / why_sim float32
         [n, k, reasons] -- per pick the `reasons` (1..8) items of the user's by_user row nearest to it by
         the cosine of the candidate factors, the score similar_items reports for the pair (include/dcue.h
         dcue_list_explain, on the device lists); short rows end in -1 / -inf. The candidate table must
-        have the fit's items."""
+        have the fit's items. item_prior: as recommend()."""
         reasons = rank.check_reasons(reasons)
         cand = self._candidates(item_factors)
         if cand.shape[0] != self.item_factors.shape[0]:
             raise ValueError("explain needs a candidate table with the fit's %d items" % self.item_factors.shape[0])
         users = np.asarray(users, dtype=np.int64).reshape(-1)
         tk = self._topk(exclude_seen, cand_mask, int(cand.shape[0]))
-        idx, score, count, flags = tk.topk_raw(self.user_factors, cand, users, k, diversity=diversity, pool=pool)
+        idx, score, count, flags = tk.topk_raw(self.user_factors, cand, users, k, diversity=diversity, pool=pool,
+                                               prior=item_prior)
         bad = (flags.cpu().numpy() & 2).astype(bool)
         if bad.any():
             raise tk._nonfinite(users, bad)
@@ -316,20 +322,20 @@ class WRMF:
         return out
 
     def recommend_for(self, histories, k=10, exclude_history=True, values=None, item_factors=None, cand_mask=None,
-                      diversity=None, pool=None, groups=None, max_per_group=None):
+                      diversity=None, pool=None, groups=None, max_per_group=None, item_prior=None):
         """recommend() for users outside the fit: fold_in(histories, values), then the inner-product
-        top-k with each history as the user's exclusion row. diversity / pool / groups / max_per_group:
-        as recommend(). Returns what recommend() returns."""
+        top-k with each history as the user's exclusion row. diversity / pool / groups / max_per_group /
+        item_prior: as recommend(). Returns what recommend() returns."""
         cand = self._candidates(item_factors)
         feat = self.fold_in(histories, values)
         ptr, idx = rank.histories_csr(histories) if exclude_history else (None, None)
         tk = rank.TopK(ptr, idx, self._mask(cand_mask), self.device, n_cand=int(cand.shape[0]), score="dot")
-        return tk.topk(feat, cand, np.arange(len(histories)), k, diversity=diversity, pool=pool,
+        return tk.topk(feat, cand, np.arange(len(histories)), k, diversity=diversity, pool=pool, prior=item_prior,
                        **self._group_kw(groups, max_per_group))
 
     def evaluate_topk(self, truth_ptr, truth_idx, ks=(10, 50, 100), users=None, exclude_ptr=None, exclude_idx=None,
                       item_factors=None, cand_mask=None, per_user=False, diversity=None, pool=None, ild=False,
-                      groups=None, max_per_group=None):
+                      groups=None, max_per_group=None, item_prior=None, item_value=None, item_tail=None, gini=False):
         """Top-K ranking quality of the inner-product lists against held-out truth rows (a CSR over
         user rows, each row sorted, no repeats): DCUE.evaluate_topk's dict -- {"precision@K",
         "recall@K", "ndcg@K", "map@K", "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} --
@@ -340,7 +346,13 @@ class WRMF:
         mean intra-list diversity of the scored lists, dcue_list_ild) and "n_ild". groups (an int array by
         candidate row) adds "groups@K", "group_top@K" and "group_coverage@K" -- DCUE.evaluate_topk's
         artist numbers (dcue_list_group_stats) -- and "n_group_lists"; with max_per_group the lists scored
-        are recommend(groups=, max_per_group=)'s."""
+        are recommend(groups=, max_per_group=)'s.
+
+        item_prior: score recommend(item_prior=)'s lists. item_value (float64 by candidate row, e.g. the
+        items' self-information) / item_tail (uint8, non-zero = long tail) add "novelty@K" and "tail@K" (the
+        mean over the lists of the first K items' mean value and tail share, dcue_list_item_stats) and
+        "n_novelty"; gini adds "gini@K", the Gini index of the candidates' exposure (dcue_exposure_gini).
+        The caller supplies the arrays: this path has no dataset to take play counts from."""
         ks = rank.check_cutoffs(ks)
         cand = self._candidates(item_factors)
         ev = rank.TopKMetrics(truth_ptr, truth_idx, self.device, excl_ptr=exclude_ptr, excl_idx=exclude_idx,
@@ -353,7 +365,7 @@ class WRMF:
         if max_per_group is not None:
             group_kw.update(self._group_kw(groups, max_per_group))
         res = ev.evaluate(self.user_factors, cand, rows, ks, per_query=per_user, diversity=diversity, pool=pool,
-                          ild=ild, **group_kw)
+                          ild=ild, prior=item_prior, item_value=item_value, item_tail=item_tail, gini=gini, **group_kw)
         out = {"n_users": res["n_evaluated"]}
         if groups is not None:
             for name, slot in (("groups", "group_distinct"), ("group_top", "group_top"),
@@ -366,6 +378,12 @@ class WRMF:
                 out["%s@%d" % (name, k)] = float(res[name][i])
         if ild:
             out["n_ild"] = res["n_ild"]
+        pop_names = (("novelty", "tail") if "novelty" in res else ()) + (("gini",) if gini else ())
+        for name in pop_names:
+            for i, k in enumerate(ks):
+                out["%s@%d" % (name, k)] = float(res[name][i])
+        if "novelty" in res:
+            out["n_novelty"] = res["n_novelty"]
         if per_user:
             out.update(users=rows.tolist(), per_user=res["per_query"], flags=res["flags"])
         return out

@@ -31,6 +31,7 @@ import torch
 from torch.utils.data import RandomSampler
 
 from dcrecommend import _native as nat
+from dcrecommend.datasets import popularity as _pop
 from dcrecommend.datasets.artists import artist_exclusion_csr, artist_groups
 from dcrecommend.datasets.csr import (check_catalogue_users, saturated_users, user_split_ranks,
                                       weighted_saturated_users, weighted_split_tables)
@@ -241,6 +242,7 @@ class DCUE(Trainer):
         self._plan_n = None
         self._evals = {}
         self._song_artist_map = None  # set_artists
+        self._popularity = None  # set_popularity: the {song_id: count} dict, or "train"
 
     # ------------------------------------------------------------------ model / optimizer
     def _init_nn(self, audio_model=None):
@@ -854,6 +856,57 @@ class DCUE(Trainer):
             self._evals[key] = artist_groups(src.item_index, amap)
         return self._evals[key]
 
+    def set_popularity(self, counts=None, head_mass=_pop.HEAD_MASS):
+        """How often each song is played: a {song_id: count} dict of non-negative integers (songs without an
+        entry count 0), read by popularity= and evaluate_topk(novelty=True). None takes the training data's
+        per-song user counts, the numbers neg_sampling='popularity' draws by. From the counts n_i over item
+        indices (datasets.popularity, float64 on the host): z_i = log2(1 + n_i) / log2(1 + max n) in [0, 1],
+        which popularity=beta scales into the serving prior float32(beta z_i); the self-information v_i =
+        -log2((n_i + 1) / sum_j (n_j + 1)), whose mean over a list is its novelty; and the long-tail bytes --
+        with the songs sorted by count descending (ties by index ascending) the head is the shortest prefix
+        holding at least head_mass of all counts, everything else is tail."""
+        self._popularity = ("train", float(head_mass)) if counts is None else (dict(counts), float(head_mass))
+        for key in [k for k in self._evals if k[0] == "popularity"]:
+            del self._evals[key]
+
+    def _popularity_arrays(self, ds):
+        """(z, self-information, tail bytes) over the item indices of ds (or the training data), cached per
+        index source."""
+        if self._popularity is None:
+            raise RuntimeError("no play counts to go by: call set_popularity() first")
+        src = self._index_source(ds)
+        key = ("popularity", id(src))
+        if key not in self._evals:
+            counts, head_mass = self._popularity
+            if isinstance(counts, str):
+                data = src if hasattr(src, "item_user") else self.train_data
+                if data is None:
+                    raise RuntimeError("set_popularity() without counts needs the interactions: pass dataset= "
+                                       "or fit() first")
+                n = np.asarray(data.item_user.tocsr().getnnz(axis=1), dtype=np.int64)
+            else:
+                n = _pop.item_counts(src.item_index, counts)
+            self._evals[key] = (_pop.log_popularity(n), _pop.self_information(n),
+                                _pop.tail_bytes(n, head_mass))
+        return self._evals[key]
+
+    def _prior_kw(self, ds, popularity_, item_prior):
+        """TopK.topk's prior argument for popularity= / item_prior= (neither: none, today's path). The array
+        is cached per (index source, beta), so that TopK keeps its device copy between calls."""
+        if popularity_ is not None and item_prior is not None:
+            raise ValueError("popularity= and item_prior= both set: pass one prior")
+        if item_prior is not None:
+            return dict(prior=item_prior)
+        if popularity_ is None:
+            return {}
+        beta = float(popularity_)
+        if not np.isfinite(beta):
+            raise ValueError("popularity must be finite, got %r" % (popularity_,))
+        key = ("popularity", id(self._index_source(ds)), beta)
+        if key not in self._evals:
+            self._evals[key] = _pop.popularity_prior(self._popularity_arrays(ds)[0], beta)
+        return dict(prior=self._evals[key])
+
     def _cap_kw(self, ds, max_per_artist, cap_rounds=4):
         """TopK.topk's group arguments for max_per_artist (None: none, today's path)."""
         if max_per_artist is None:
@@ -866,7 +919,7 @@ class DCUE(Trainer):
                 for r in range(len(count))]
 
     def recommend(self, users, k=10, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None,
-                  max_per_artist=None, new_artists=False, cap_rounds=4):
+                  max_per_artist=None, new_artists=False, cap_rounds=4, popularity=None, item_prior=None):
         """The k best songs for each user id, by the cosine of DCUE.score: one list per user of
         (song_id, score) pairs, best first (as_ids=False: the raw (idx [n, k], score [n, k],
         count [n]) arrays over item indices). Candidates are the dataset's (or loader's) split songs,
@@ -885,29 +938,39 @@ class DCUE(Trainer):
         leaves short are ranked deeper, at most cap_rounds - 1 times, and then equal the cap applied to
         the user's full ranking). A list can still come back shorter than k when the rounds or the
         catalogue run out. With diversity= the pool is capped before MMR picks from it. new_artists: the
-        songs of every artist the user has played in any split are left out, played or not."""
+        songs of every artist the user has played in any split are left out, played or not.
+
+        popularity (beta; None: the plain cosine; needs set_popularity): every song's score gets the prior
+        float32(beta z_i) added inside the fused ranking (dcue_topk_prior), z_i the song's scaled
+        log-popularity in [0, 1] -- beta < 0 demotes the hits, beta > 0 promotes them, and the scores
+        returned are the sums. item_prior: any finite array over item indices instead (boosts, recency, item
+        biases); passing both raises ValueError. The prior reaches the pool of diversity= (whose relevance
+        is then min-max scaled) and every round of max_per_artist=."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         index = self._index_source(ds).user_index
         rows = np.array([index[u] for u in users], dtype=np.int64)
         cap_kw = self._cap_kw(ds, max_per_artist, cap_rounds)
+        cap_kw.update(self._prior_kw(ds, popularity, item_prior))
         out = self._topk("user", ds, exclude_seen, by_artist=new_artists).topk(
             self.user_factors, self._item_feat_by_index(), rows, k, diversity=diversity, pool=pool, **cap_kw)
         return self._as_pairs(ds, *out) if as_ids else out
 
-    def recommend_artists(self, users, k=10, dataset=None, exclude_seen=True, new_artists=False, cap_rounds=4):
+    def recommend_artists(self, users, k=10, dataset=None, exclude_seen=True, new_artists=False, cap_rounds=4,
+                          popularity=None, item_prior=None):
         """The k best ARTISTS for each user id: per user a list of (artist, best_song_id, score) triples,
         artists ranked by their best eligible song -- recommend(max_per_artist=1) over the songs with a
         known artist, mapped through the artists' names. Exact when no list comes back short of k (the
         deepening rounds, cap_rounds - 1 at the most, reached k artists or the end of the catalogue).
-        exclude_seen / new_artists: as recommend()."""
+        exclude_seen / new_artists / popularity / item_prior: as recommend()."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         src = self._index_source(ds)
         group_of, names = self._artist_groups(ds)
         rows = np.array([src.user_index[u] for u in users], dtype=np.int64)
         idx, score, count = self._topk("user", ds, exclude_seen, by_artist=new_artists, with_artist=True).topk(
-            self.user_factors, self._item_feat_by_index(), rows, k, **self._cap_kw(ds, 1, cap_rounds))
+            self.user_factors, self._item_feat_by_index(), rows, k, **self._cap_kw(ds, 1, cap_rounds),
+            **self._prior_kw(ds, popularity, item_prior))
         songs = src.itemindex2songid
         return [[(names[int(group_of[i])], songs[int(i)], float(s)) for i, s in zip(idx[r, :count[r]], score[r, :count[r]])]
                 for r in range(len(count))]
@@ -936,7 +999,7 @@ class DCUE(Trainer):
                  for j in range(count[r])] for r in range(len(count))]
 
     def explain(self, users, k=10, reasons=3, dataset=None, exclude_seen=True, as_ids=True, diversity=None, pool=None,
-                max_per_artist=None, new_artists=False):
+                max_per_artist=None, new_artists=False, popularity=None, item_prior=None):
         """recommend()'s lists with the reason for every pick: per user a list of (song_id, score,
         [(history_song_id, similarity), ...]) triples -- the picks and scores are recommend()'s, bit for
         bit (the same dcue_topk call), and the `reasons` (1..8) history songs are those of the user's
@@ -944,8 +1007,8 @@ class DCUE(Trainer):
         similar_songs reports for the pair (include/dcue.h dcue_list_explain, one launch on the device
         lists). A user without such a song gets empty reason lists. as_ids=False: the raw (idx [n, k],
         score [n, k], count [n], why_idx [n, k, reasons], why_sim [n, k, reasons]) arrays over item
-        indices, short rows ending in -1 / -inf. diversity / pool / max_per_artist / new_artists: as
-        recommend()."""
+        indices, short rows ending in -1 / -inf. diversity / pool / max_per_artist / new_artists / popularity /
+        item_prior: as recommend() (the reasons' similarities stay plain cosines)."""
         reasons = rank.check_reasons(reasons)
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
@@ -963,7 +1026,7 @@ class DCUE(Trainer):
                 self._evals[key] = rank._upload_csr(*src.user_item_csr(), self.device)
             hist = self._evals[key]
         return self._explained(tk, ds, self.user_factors, rows, k, reasons, diversity, pool, *hist, as_ids,
-                               self._cap_kw(ds, max_per_artist))
+                               dict(self._cap_kw(ds, max_per_artist), **self._prior_kw(ds, popularity, item_prior)))
 
     def similar_songs(self, songs, k=10, dataset=None, max_per_artist=None, other_artists=False, pool=None):
         """The k songs most similar to each song id (item-to-item on the same kernel: the item factors
@@ -1095,7 +1158,7 @@ class DCUE(Trainer):
         return self._evals[key]
 
     def evaluate_topk(self, dataset=None, ks=(10, 50, 100), users=None, per_user=False, diversity=None, pool=None,
-                      ild=False, artists=False, max_per_artist=None):
+                      ild=False, artists=False, max_per_artist=None, popularity=None, item_prior=None, novelty=False):
         """Top-K ranking quality of the current factors: {"precision@K", "recall@K", "ndcg@K", "map@K",
         "mrr@K", "hit@K", "coverage@K" for each K of ks, "n_users"} (include/dcue.h dcue_topk_metrics
         has the definitions). Candidates are the dataset's (or loader's) split songs with audio, or
@@ -1117,7 +1180,14 @@ class DCUE(Trainer):
         number of distinct artists among a list's first K songs, a song without an artist counting as one
         of its own), "artist_top@K" (the mean of the most songs one artist holds there) and
         "artist_coverage@K" (the share of the artists with a candidate song that appear in some list's
-        first K), by dcue_list_group_stats on the same device lists, and "n_artist_lists"."""
+        first K), by dcue_list_group_stats on the same device lists, and "n_artist_lists".
+
+        popularity / item_prior: score recommend(popularity=) / recommend(item_prior=)'s lists, the ones that
+        would be served. novelty (needs set_popularity) adds "novelty@K" (the mean over the lists of the
+        first K songs' mean self-information, in bits: higher = further from the hits), "tail@K" (the mean
+        share of long-tail songs among them), both by dcue_list_item_stats on the same device lists, with
+        "n_novelty" the lists behind them, and "gini@K" (the Gini index of the candidates' exposure in the
+        lists' first K entries: 0 = all served equally often; dcue_exposure_gini)."""
         ks = rank.check_cutoffs(ks)
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
@@ -1132,6 +1202,10 @@ class DCUE(Trainer):
         cap_kw = self._cap_kw(ds, max_per_artist)
         if artists:
             cap_kw.update(group_of=self._artist_groups(ds)[0], group_stats=True)
+        cap_kw.update(self._prior_kw(ds, popularity, item_prior))
+        if novelty:
+            _, value, tail = self._popularity_arrays(ds)
+            cap_kw.update(item_value=value, item_tail=tail, gini=True)
         res = ev.evaluate(self.user_factors, self._item_feat_by_index(), rows, ks, per_query=per_user,
                           diversity=diversity, pool=pool, ild=ild, **cap_kw)
         out = {"n_users": res["n_evaluated"]}
@@ -1146,6 +1220,11 @@ class DCUE(Trainer):
             out["n_artist_lists"] = res["n_group"]
         if ild:
             out["n_ild"] = res["n_ild"]
+        if novelty:
+            for name in ("novelty", "tail", "gini"):
+                for i, k in enumerate(ks):
+                    out["%s@%d" % (name, k)] = float(res[name][i])
+            out["n_novelty"] = res["n_novelty"]
         if per_user:
             out.update(users=users, per_user=res["per_query"], flags=res["flags"])
         return out
@@ -1212,11 +1291,13 @@ class DCUE(Trainer):
         return emb, feat, loss
 
     def recommend_for(self, histories, k=10, dataset=None, exclude_history=True, as_ids=True, diversity=None,
-                      pool=None, max_per_artist=None, new_artists=False, **fold_in_kwargs):
+                      pool=None, max_per_artist=None, new_artists=False, popularity=None, item_prior=None,
+                      **fold_in_kwargs):
         """recommend() for users outside the trained table: fold_in(histories, **fold_in_kwargs), then
         the fused top-k pass with each history as the user's exclusion list (every song of it, with
         or without audio). diversity / pool / max_per_artist: as recommend(); new_artists: the songs of
-        every artist in the history are left out. Returns what recommend() returns."""
+        every artist in the history are left out; popularity / item_prior: as recommend(). Returns what
+        recommend() returns."""
         self._require_factors()
         ds = None if dataset is None else _dataset(dataset)
         usable, full = self._history_items(histories, ds)
@@ -1229,7 +1310,7 @@ class DCUE(Trainer):
         ptr, idx = self._history_exclusion(ds, full, exclude_history, new_artists)
         out = rank.TopK(ptr, idx, self._cand_mask(ds), self.device).topk(
             feat, self._item_feat_by_index(), np.arange(len(full)), k, diversity=diversity, pool=pool,
-            **self._cap_kw(ds, max_per_artist))
+            **self._cap_kw(ds, max_per_artist), **self._prior_kw(ds, popularity, item_prior))
         return self._as_pairs(ds, *out) if as_ids else out
 
     def _history_exclusion(self, ds, full, exclude_history, new_artists):
@@ -1241,7 +1322,8 @@ class DCUE(Trainer):
         return hist if exclude_history else (None, None)
 
     def explain_for(self, histories, k=10, reasons=3, dataset=None, exclude_history=True, as_ids=True, diversity=None,
-                    pool=None, max_per_artist=None, new_artists=False, **fold_in_kwargs):
+                    pool=None, max_per_artist=None, new_artists=False, popularity=None, item_prior=None,
+                    **fold_in_kwargs):
         """recommend_for() with the reason for every pick: the lists are recommend_for()'s (the same
         fold-in and dcue_topk calls), the reasons the `reasons` (1..8) songs of each given history that
         have audio, nearest to the pick by the cosine of the item factors. Returns what explain() returns."""
@@ -1258,7 +1340,8 @@ class DCUE(Trainer):
         ptr, idx = self._history_exclusion(ds, full, exclude_history, new_artists)
         tk = rank.TopK(ptr, idx, self._cand_mask(ds), self.device)
         return self._explained(tk, ds, feat, np.arange(len(full)), k, reasons, diversity, pool,
-                               *rank.histories_csr(usable), as_ids, self._cap_kw(ds, max_per_artist))
+                               *rank.histories_csr(usable), as_ids,
+                               dict(self._cap_kw(ds, max_per_artist), **self._prior_kw(ds, popularity, item_prior)))
 
     def _compute_scores(self, split, pred_loader, truth_loader, train_data, val_data, test_data, pct=0.025):
         """nn/dcue.py:580-603."""

@@ -21,6 +21,10 @@ history nearest to it by the cosine similar_songs reports, on the same device li
 GroupCap (dcue_list_group_cap / dcue_list_group_stats) knows who made a song: at most so many entries per
 group (artist, album, label) of TopK's device lists, and how many groups a list spans.
 
+TopK's prior= (dcue_topk_prior) adds a per-candidate term to every score inside the fused ranking --
+popularity promotion or demotion, boosts, item biases -- and PopStats (dcue_list_item_stats /
+dcue_exposure_gini) says where the lists sit on that trade-off: novelty, long-tail share, exposure Gini.
+
 FoldIn (dcue_user_foldin) gives users outside the trained table a factor: one embedding row per user
 learned against the frozen towers, all steps in one kernel launch.
 """
@@ -216,6 +220,7 @@ class TopK(_Workspace):
     _gcap = None  # the GroupCap of max_per_group= calls, likewise
     _groups = None  # (the caller's group_of, its device copy, n_groups) of the last max_per_group= call
     _excl_np = None  # the exclusion CSR's host copy, for deepening rounds
+    _prior = None  # (the caller's prior, its device copy) of the last prior= call
     cap_rounds_used = 0  # ranking rounds of the last max_per_group= call (1: no list was deepened)
 
     def __init__(self, excl_ptr, excl_idx, cand_mask, device, n_cand=None, score="cosine"):
@@ -234,17 +239,33 @@ class TopK(_Workspace):
     def _nonfinite(self, queries, bad):
         return (_nonfinite_error if self.score == nat.SCORE_COSINE else _nonfinite_dot_error)(queries, bad)
 
+    def _prior_arg(self, prior):
+        """The float32 [n_cand] device copy of a prior= array or tensor (None stays None); the upload is kept
+        for the next call with the same object. Finiteness is checked once, on the host array, before it."""
+        if prior is None:
+            return None
+        if self._prior is None or self._prior[0] is not prior:
+            host = prior.detach().cpu().numpy() if torch.is_tensor(prior) else np.asarray(prior)
+            host = np.ascontiguousarray(host, dtype=np.float32).reshape(-1)
+            if host.size != self.n_cand:
+                raise ValueError("prior has %d entries for %d candidates" % (host.size, self.n_cand))
+            if not np.isfinite(host).all():
+                raise ValueError("prior is not finite at candidate %d" % int(np.argmin(np.isfinite(host))))
+            self._prior = (prior, torch.from_numpy(host).to(self.device))
+        return self._prior[1]
+
     def _diverse_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel,
-                     groups=None):
+                     groups=None, prior=None):
         """topk_raw at k = pool, then Diversify.mmr_raw down to k. The flags are dcue_topk's; a list MMR
         found non-finite (nat.LIST_FLAG_NONFINITE) carries dcue_topk's bit for it. groups (_group_args): the
         pool is capped per group before MMR sees it."""
         k, pool = check_pool(k, pool)
-        if rel is None:
-            rel = "raw" if self.score == nat.SCORE_COSINE else "minmax"
+        if rel is None:  # (with a prior the sum is no longer on the similarity's scale)
+            rel = "raw" if self.score == nat.SCORE_COSINE and prior is None else "minmax"
         if self._div is None:
             self._div = Diversify(self.device)
-        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split)
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split,
+                                                 prior=prior)
         gflags = None
         if groups is not None:  # MMR picks from a pool that already satisfies the cap, so its output does too
             idx, score, count, _, gflags = self._cap().cap_raw(idx, score, count, *groups, pool)
@@ -283,7 +304,8 @@ class TopK(_Workspace):
             self._excl_np = (self.excl_ptr.cpu().numpy(), self.excl_idx.cpu().numpy())
         return self._excl_np if self._excl_np is not None else (None, None)
 
-    def _capped_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, pool, groups, cap_rounds):
+    def _capped_raw(self, query_feat, cand_feat, queries, k, query_batch, cand_split, pool, groups, cap_rounds,
+                    prior=None):
         """topk_raw at k = pool, GroupCap.cap_raw down to k, and up to cap_rounds - 1 deepening rounds for
         the lists the cap left short of k while their pool was full: those lists' query rows are ranked
         again at k = pool with everything ranked so far added to their exclusion rows -- a score is a
@@ -293,7 +315,8 @@ class TopK(_Workspace):
         on the host (the rare path)."""
         k, pool = check_pool(k, pool)
         queries = np.asarray(queries, dtype=np.int64).reshape(-1)
-        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split)
+        idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, pool, query_batch, cand_split,
+                                                 prior=prior)
         gc = self._cap()
         oidx, oscore, ocount, _, gflags = gc.cap_raw(idx, score, count, *groups, k)
         self.cap_rounds_used = 1
@@ -313,7 +336,8 @@ class TopK(_Workspace):
             deeper = TopK(*histories_csr(excl), self.cand_mask, self.device, n_cand=self.n_cand,
                           score=[s for s, v in nat.SCORES.items() if v == self.score][0])
             didx, dscore, dcount, dflags = deeper.topk_raw(query_feat.index_select(0, qrows), cand_feat,
-                                                           np.arange(len(rows_np)), pool, query_batch, cand_split)
+                                                           np.arange(len(rows_np)), pool, query_batch, cand_split,
+                                                           prior=prior)
             carry = (oidx.index_select(0, rows), oscore.index_select(0, rows), ocount.index_select(0, rows))
             nidx, nscore, ncount, _, nflags = gc.cap_raw(didx, dscore, dcount, *groups, k, carry=carry)
             idx[rows], count[rows] = didx, dcount  # the pools the next round continues from
@@ -322,7 +346,7 @@ class TopK(_Workspace):
         return oidx, oscore, ocount, flags | (gflags & (nat.GROUP_FLAG_SHORT | nat.GROUP_FLAG_BAD_GROUP))
 
     def topk_raw(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
-                 rel=None, group_of=None, max_per_group=None, cap_rounds=4):
+                 rel=None, group_of=None, max_per_group=None, cap_rounds=4, prior=None):
         """(idx int32 [n, k], score float32 [n, k], count int32 [n], flags int32 [n]) device tensors,
         as dcue_topk writes them (no non-finite check).
 
@@ -339,20 +363,28 @@ class TopK(_Workspace):
         pool was full are deepened, at most cap_rounds - 1 times (_capped_raw). flags then also carries
         nat.GROUP_FLAG_SHORT (fewer than k entries: the catalogue or the rounds ran out) and
         GROUP_FLAG_BAD_GROUP. With diversity= the pool is capped first and MMR picks from the capped pool,
-        without deepening."""
+        without deepening.
+
+        prior (None: today's path exactly): a float array or tensor [n_cand] added to every score of its
+        candidate inside the fused ranking (include/dcue.h dcue_topk_prior): s = fl32(s0 + prior[c]), and
+        the scores returned are the sums. It reaches every ranking the call makes -- the pool of
+        diversity=, the first round and the deepening rounds of max_per_group= -- and with it rel defaults
+        to "minmax" in both score modes. A non-finite entry raises ValueError before anything is uploaded."""
+        prior_dev = self._prior_arg(prior)
         if max_per_group is not None:
             groups = self._group_args(group_of, max_per_group, cap_rounds)
             if diversity is not None:
                 return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool,
-                                         rel, groups)
+                                         rel, groups, prior)
             if rel is not None:
                 raise ValueError("rel belongs to diversity=, which is not set")
             return self._capped_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, pool, groups,
-                                    cap_rounds)
+                                    cap_rounds, prior)
         if group_of is not None:
             raise ValueError("group_of belongs to max_per_group=, which is not set")
         if diversity is not None:
-            return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel)
+            return self._diverse_raw(query_feat, cand_feat, queries, k, query_batch, cand_split, diversity, pool, rel,
+                                     prior=prior)
         if pool is not None or rel is not None:
             raise ValueError("pool and rel belong to diversity= (pool also to max_per_group=), which is not set")
         nat.require_gpu(query_feat, "query_feat")
@@ -379,24 +411,28 @@ class TopK(_Workspace):
                     nat.ptr(self.excl_ptr), nat.ptr(self.excl_idx), nat.ptr(self.cand_mask), k, qb, int(cand_split),
                     nat.ptr(ws), ws.numel(), nat.ptr(idx), nat.ptr(score), nat.ptr(count), nat.ptr(flags),
                     nat.stream_handle(self.device))
-            if self.score == nat.SCORE_COSINE:
+            if prior_dev is not None:
+                nat.check(nat.lib().dcue_topk_prior(self.score, *args[:10], nat.ptr(prior_dev), *args[10:]),
+                          "dcue_topk_prior")
+            elif self.score == nat.SCORE_COSINE:
                 nat.check(nat.lib().dcue_topk(*args), "dcue_topk")
             else:
                 nat.check(nat.lib().dcue_topk_scored(self.score, *args), "dcue_topk_scored")
         return idx[:nq], score[:nq], count[:nq], flags[:nq]
 
     def topk(self, query_feat, cand_feat, queries, k, query_batch=None, cand_split=0, diversity=None, pool=None,
-             rel=None, group_of=None, max_per_group=None, cap_rounds=4):
+             rel=None, group_of=None, max_per_group=None, cap_rounds=4, prior=None):
         """(idx int64 [n, k], score float32 [n, k], count int32 [n]) numpy arrays, best first; rows
         with fewer than k eligible candidates end in idx -1 / score -inf. diversity / pool / rel: as
         topk_raw (the lists are then in MMR's selection order, not sorted by score). group_of /
         max_per_group / cap_rounds: as topk_raw; a group id outside -1 .. n_groups - 1 raises ValueError.
+        prior: as topk_raw (the scores are then the sums).
 
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite: a diverged model fails here as it fails in DCUE.score (score="dot": the factors are
         not finite or the product overflowed)."""
         idx, score, count, flags = self.topk_raw(query_feat, cand_feat, queries, k, query_batch, cand_split,
-                                                 diversity, pool, rel, group_of, max_per_group, cap_rounds)
+                                                 diversity, pool, rel, group_of, max_per_group, cap_rounds, prior)
         flags = flags.cpu().numpy()
         bad = (flags & 2).astype(bool)
         if bad.any():
@@ -685,6 +721,114 @@ class GroupCap(_Workspace):
         return mean, cov, n_eval
 
 
+class PopStats(_Workspace):
+    """Popularity-bias statistics of the lists dcue_topk / dcue_list_mmr / dcue_list_group_cap leave on the
+    device (include/dcue.h dcue_list_item_stats / dcue_list_item_stats_mean / dcue_exposure_gini): device
+    tensors in and out, no list is copied to the host.
+
+    item_value float64 [n_cand] (None: the column is 0): a per-item number prepared on the host -- the
+    self-information of DCUE.set_popularity gives novelty; item_tail uint8 [n_cand] (None: 0): non-zero
+    for a long-tail item."""
+
+    def __init__(self, device, n_cand, item_value=None, item_tail=None):
+        self.device = torch.device(device)
+        self.n_cand = int(n_cand)
+        self.item_value = self._column(item_value, torch.float64, np.float64, "item_value")
+        self.item_tail = self._column(item_tail, torch.uint8, np.uint8, "item_tail")
+
+    def _column(self, a, tdtype, ndtype, name):
+        if a is None:
+            return None
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=ndtype))
+        t = t.to(self.device, tdtype).contiguous().reshape(-1)
+        if t.numel() != self.n_cand:
+            raise ValueError("%s has %d entries for %d candidates" % (name, t.numel(), self.n_cand))
+        return t
+
+    def _stats_into(self, idx, count, ks, cut, out, flags):
+        """dcue_list_item_stats on checked device lists, writing out [n, m, 2] / flags [n] (views of the
+        caller's buffers)."""
+        n, k = int(idx.shape[0]), int(idx.shape[1])
+        if ks[-1] > k:
+            raise ValueError("cutoff %d is beyond the lists' k = %d" % (ks[-1], k))
+        if n:
+            nat.check(nat.lib().dcue_list_item_stats(
+                nat.ptr(idx), nat.ptr(count), n, k, nat.ptr(self.item_value), nat.ptr(self.item_tail), self.n_cand,
+                ctypes.cast(cut, ctypes.c_void_p), len(ks), nat.ptr(out), nat.ptr(flags),
+                nat.stream_handle(self.device)), "dcue_list_item_stats")
+
+    def stats_raw(self, idx, count, ks):
+        """(stats float64 [n, m, 2], flags int32 [n]) device tensors for the lists idx int32 [n, k] / count
+        int32 [n] at the sorted distinct cutoffs of ks: per cutoff K the mean item_value and the share of
+        tail items among the first min(K, count) entries. flags: nat.ITEM_FLAG_EMPTY / LIST_FLAG_BAD_INDEX
+        (such a list has zeros and is left out of the means)."""
+        ks = check_cutoffs(ks)
+        cut = (ctypes.c_int32 * len(ks))(*ks)
+        nat.require_gpu(idx, "idx")
+        nat.require_gpu(count, "count")
+        if idx.dim() != 2 or idx.dtype != torch.int32 or count.dtype != torch.int32 or count.numel() != idx.shape[0]:
+            raise ValueError("idx must be int32 [n, k] and count int32 [n]")
+        if not 1 <= idx.shape[1] <= nat.TOPK_MAX_K:
+            raise ValueError("k must be in 1..%d, got %d" % (nat.TOPK_MAX_K, idx.shape[1]))
+        n = int(idx.shape[0])
+        out = torch.zeros((max(n, 1), len(ks), nat.ITEM_N_STATS), dtype=torch.float64, device=self.device)
+        flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
+        self._stats_into(idx.contiguous(), count.contiguous(), ks, cut, out, flags)
+        return out[:n], flags[:n]
+
+    def mean_raw(self, stats, flags):
+        """(mean float64 [m, 2], n_evaluated int32 [1]) device tensors: dcue_list_item_stats_mean over stats
+        [n, m, 2] / flags [n] -- the mean over the unflagged lists, in an order that depends on n and m only."""
+        nat.require_gpu(stats, "stats")
+        nat.require_gpu(flags, "flags")
+        if (stats.dim() != 3 or stats.shape[2] != nat.ITEM_N_STATS or stats.dtype != torch.float64
+                or flags.dtype != torch.int32 or flags.numel() != stats.shape[0]):
+            raise ValueError("stats must be float64 [n, m, 2] and flags int32 [n]")
+        n, m = int(stats.shape[0]), int(stats.shape[1])
+        if not 1 <= m <= nat.TOPK_METRICS_MAX_CUTOFFS:
+            raise ValueError("at most %d cutoffs per call, got %d" % (nat.TOPK_METRICS_MAX_CUTOFFS, m))
+        mean = torch.zeros((m, nat.ITEM_N_STATS), dtype=torch.float64, device=self.device)
+        n_eval = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if n == 0:  # (an empty tensor's address may be null)
+            stats = torch.zeros((1, m, nat.ITEM_N_STATS), dtype=torch.float64, device=self.device)
+            flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        nat.check(nat.lib().dcue_list_item_stats_mean(nat.ptr(stats.contiguous()), nat.ptr(flags.contiguous()), n, m,
+                                                      nat.ptr(mean), nat.ptr(n_eval), nat.stream_handle(self.device)),
+                  "dcue_list_item_stats_mean")
+        return mean, n_eval
+
+    def gini_raw(self, exposure, n_lists_max, cand_mask=None):
+        """(gini float64 [m], total int64 [m]) device tensors: the Gini index of the exposure counts
+        (int32 [m, n_cand] on the device, as dcue_topk_metrics accumulates them; cutoff i counts the
+        positions below it, as coverage does) over the candidates cand_mask (uint8 [n_cand] on the device;
+        None: all) admits, and the exposure they sum to. n_lists_max: the lists that added to `exposure`;
+        a count above it gives total -1 (gini raises for it)."""
+        nat.require_gpu(exposure, "exposure")
+        if exposure.dim() != 2 or exposure.dtype != torch.int32 or exposure.shape[1] != self.n_cand:
+            raise ValueError("exposure must be int32 [m, %d]" % self.n_cand)
+        m = int(exposure.shape[0])
+        if not 1 <= m <= nat.TOPK_METRICS_MAX_CUTOFFS:
+            raise ValueError("at most %d cutoffs per call, got %d" % (nat.TOPK_METRICS_MAX_CUTOFFS, m))
+        if cand_mask is not None and (cand_mask.dtype != torch.uint8 or cand_mask.numel() != self.n_cand):
+            raise ValueError("cand_mask must be uint8 [%d]" % self.n_cand)
+        nbytes = self._nbytes("dcue_exposure_gini_workspace_bytes", self.n_cand, m, int(n_lists_max))
+        ws = self._grow(nbytes)
+        gini = torch.zeros(m, dtype=torch.float64, device=self.device)
+        total = torch.zeros(m, dtype=torch.int64, device=self.device)
+        nat.check(nat.lib().dcue_exposure_gini(
+            nat.ptr(exposure.contiguous()), nat.ptr(cand_mask.contiguous() if cand_mask is not None else None),
+            self.n_cand, m, nat.ptr(ws), nbytes, nat.ptr(gini), nat.ptr(total), nat.stream_handle(self.device)),
+            "dcue_exposure_gini")
+        return gini, total
+
+    def gini(self, exposure, n_lists_max, cand_mask=None):
+        """gini_raw's index as a float64 numpy array; ValueError where a count lies outside 0..n_lists_max."""
+        g, total = self.gini_raw(exposure, n_lists_max, cand_mask)
+        if (total.cpu().numpy() < 0).any():
+            raise ValueError("an exposure count is negative or above n_lists_max = %d" % int(n_lists_max))
+        return g.cpu().numpy()
+
+
 def check_reasons(reasons):
     """`reasons` as an int in 1..EXPLAIN_MAX_REASONS; ValueError naming the limit otherwise."""
     m = int(reasons)
@@ -848,7 +992,8 @@ class TopKMetrics(_Workspace):
         return mean, cov, n_eval
 
     def evaluate(self, query_feat, cand_feat, queries, ks, query_batch=None, per_query=False, diversity=None,
-                 pool=None, rel=None, ild=False, group_of=None, max_per_group=None, cap_rounds=4, group_stats=False):
+                 pool=None, rel=None, ild=False, group_of=None, max_per_group=None, cap_rounds=4, group_stats=False,
+                 prior=None, item_value=None, item_tail=None, gini=False):
         """{"ks", "n_evaluated", "precision", "recall", "ndcg", "map", "mrr", "hit", "coverage"}: each
         metric a float64 array over the cutoffs, the mean over the queries with a non-empty truth row;
         per_query adds "per_query" (numpy [n, m, 6], slots in nat.TOPK_METRIC_NAMES order) and "flags".
@@ -866,6 +1011,16 @@ class TopKMetrics(_Workspace):
         "group_coverage" (the share of the groups that have a candidate which appear in some list's first
         K entries) and "n_group" (the lists behind them), by dcue_list_group_stats /
         dcue_list_group_stats_mean on the same device lists.
+
+        prior: the lists are TopK.topk_raw's with that per-candidate prior (None scores today's lists).
+        item_value (float64 [n_cand]) / item_tail (uint8 [n_cand]), either or both: add "novelty" and "tail"
+        (float64 over the cutoffs: the mean over the non-empty lists of the first K entries' mean item_value
+        -- the self-information gives novelty -- and of their share of tail items; a column that was not
+        given is 0) and "n_novelty" (the lists behind them), by dcue_list_item_stats /
+        dcue_list_item_stats_mean on the same device lists. gini adds "gini" (float64 over the cutoffs: the
+        Gini index of the candidates' exposure in the evaluated lists' first K entries, 0 = every candidate
+        served equally often, towards 1 = a few candidates hold all of it), by dcue_exposure_gini on the
+        exposure counts coverage is read from.
 
         Raises ValueError in the evaluator's wording when an eligible candidate's score is NaN or
         infinite, as TopK.topk does."""
@@ -885,6 +1040,11 @@ class TopKMetrics(_Workspace):
             g_out = torch.zeros((max(n, 1), m, nat.GROUP_N_STATS), dtype=torch.int32, device=self.device)
             g_flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
             g_exposure = gc.new_exposure(m, n_groups)
+        pop = None
+        if item_value is not None or item_tail is not None or gini:
+            pop = PopStats(self.device, self.n_cand, item_value, item_tail)
+            p_out = torch.zeros((max(n, 1), m, nat.ITEM_N_STATS), dtype=torch.float64, device=self.device)
+            p_flags = torch.zeros(max(n, 1), dtype=torch.int32, device=self.device)
         if self.topk.excl_ptr is None and query_feat.shape[0] != self.n_query_rows:
             raise ValueError("query factors have %d rows, the truth CSR %d" % (query_feat.shape[0], self.n_query_rows))
         qb = int(self.topk.DEFAULT_QUERY_BATCH if query_batch is None else query_batch)
@@ -901,10 +1061,11 @@ class TopKMetrics(_Workspace):
         for q0 in range(0, n, qb):
             part = queries[q0:q0 + qb]
             if diversity is None and not cap_kw:
-                idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb)
+                idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb, prior=prior)
             else:
                 idx, _, count, tflags = self.topk.topk_raw(query_feat, cand_feat, part, k, query_batch=qb,
-                                                           diversity=diversity, pool=pool, rel=rel, **cap_kw)
+                                                           diversity=diversity, pool=pool, rel=rel, prior=prior,
+                                                           **cap_kw)
             q = torch.as_tensor(part.astype(np.int32)).to(self.device)
             self._metrics_into(idx, count, q, cut, m, out[q0:], flags[q0:], exposure)
             nonfinite[q0:q0 + len(part)] = tflags
@@ -914,6 +1075,8 @@ class TopKMetrics(_Workspace):
             if group_stats:
                 gc._stats_into(idx.contiguous(), count.contiguous(), g_dev, n_groups, ks, cut, g_out[q0:],
                                g_flags[q0:], g_exposure)
+            if pop is not None and (item_value is not None or item_tail is not None):
+                pop._stats_into(idx.contiguous(), count.contiguous(), ks, cut, p_out[q0:], p_flags[q0:])
         bad = (nonfinite[:n].cpu().numpy() & 2).astype(bool)
         if bad.any():
             raise self.topk._nonfinite(queries, bad)
@@ -936,6 +1099,12 @@ class TopKMetrics(_Workspace):
             g_mean = g_mean.cpu().numpy()
             res.update(group_distinct=g_mean[:, 0].copy(), group_top=g_mean[:, 1].copy(),
                        group_coverage=g_cov.cpu().numpy(), n_group=int(n_g.cpu().numpy()[0]))
+        if pop is not None and (item_value is not None or item_tail is not None):
+            p_mean, n_p = pop.mean_raw(p_out[:n], p_flags[:n])
+            p_mean = p_mean.cpu().numpy()
+            res.update(novelty=p_mean[:, 0].copy(), tail=p_mean[:, 1].copy(), n_novelty=int(n_p.cpu().numpy()[0]))
+        if gini:
+            res["gini"] = pop.gini(exposure, max(n, 1), self.cand_mask)  # (a list names a candidate once)
         if per_query:
             res["per_query"] = out[:n].cpu().numpy()
             res["flags"] = flags[:n].cpu().numpy()

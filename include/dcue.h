@@ -722,6 +722,29 @@ int dcue_topk_scored(int32_t score, const float* query_feat, int64_t n_query_row
                      const int64_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand_mask, int32_t k,
                      int32_t query_batch, int32_t cand_split, void* ws, size_t ws_bytes, int32_t* out_idx,
                      float* out_score, int32_t* out_count, int32_t* out_flags, void* stream);
+/* (added under ABI 17) dcue_topk_scored with an additive per-candidate prior -- popularity promotion or
+ * demotion, editorial boosts, recency, a matrix factorisation's item biases. cand_prior follows
+ * cand_mask, the other per-candidate array; every other argument, the workspace
+ * (dcue_topk_workspace_bytes: the prior needs none) and every rule above unchanged:
+ *   cand_prior float [n_cand] (device), or null: the call is then dcue_topk_scored -- the same kernels,
+ *     the same bits.
+ *   Score: s = fl32(s0 + cand_prior[c]), where s0 is the score dcue_topk_scored produces for the pair
+ *     (its -0 already +0); the sum's -0 is folded to +0 again before keying. It is ONE fp32 addition
+ *     after the MFMA accumulators are final, never a term of their sum: s is a function of (s0's bits,
+ *     the prior) alone, so the lists still do not depend on query_batch or cand_split, bit for bit.
+ *   out_score is the sum, the number the list was ranked by. Key, order (score descending, then index
+ *     ascending), mask, exclusion CSR, padding, out_count and the merge are dcue_topk's.
+ *   out_flags[q] bit 1: an eligible candidate's SUM is NaN or infinite -- a non-finite s0, a non-finite
+ *     prior, or an overflow of the addition. A NaN is never returned; +-inf order as ordinary values. The
+ *     prior of a candidate the mask or the query's exclusion row removes is never looked at.
+ * Validated on the host before the first device call as dcue_topk_scored is, each refusal with a
+ * dcue_last_error text. Synchronises `stream` before returning. */
+int dcue_topk_prior(int32_t score, const float* query_feat, int64_t n_query_rows, const float* cand_feat,
+                    int64_t n_cand, int32_t d, const int32_t* queries, int32_t n_queries,
+                    const int64_t* excl_ptr, const int32_t* excl_idx, const uint8_t* cand_mask,
+                    const float* cand_prior, int32_t k, int32_t query_batch, int32_t cand_split, void* ws,
+                    size_t ws_bytes, int32_t* out_idx, float* out_score, int32_t* out_count, int32_t* out_flags,
+                    void* stream);
 
 /* ------------------------------------------------------------ WRMF objective (added under ABI 17) */
 /* The objective the ALS half-steps (dcue_wrmf_half_step) descend,
@@ -1284,6 +1307,61 @@ int dcue_list_group_stats_mean(const int32_t* stats, const int32_t* flags, int32
                                const int32_t* group_exposure, const uint8_t* group_present, int32_t n_groups,
                                double* out_mean /* [m][2] */, double* out_coverage, int32_t* out_n_evaluated,
                                void* stream);
+
+/* ------------------- popularity-bias statistics: novelty, long-tail share, exposure Gini (added under ABI 17) */
+/* How far served lists lean on the catalogue's hits, on the lists dcue_topk / dcue_topk_scored /
+ * dcue_topk_prior / dcue_list_mmr / dcue_list_group_cap leave on the device. The reference has no
+ * counterpart.
+ * Item statistics. idx [n_lists][k] / count [n_lists]: those calls' out_idx / out_count, 1 <= k <=
+ *   DCUE_TOPK_MAX_K; c = count clamped to 0..k. Entries at j >= c are never read.
+ *   item_value double [n_cand] (device; nullable): a per-item number the HOST prepared -- the
+ *     self-information -log2 p_i of an item's share of all plays gives novelty. No transcendental runs
+ *     on the device. item_tail uint8 [n_cand] (device; nullable): non-zero = a long-tail item. A null
+ *     array's column is 0.
+ *   For a cutoff K, n_K = min(K, c): value@K = (sum over j < n_K of item_value[L[j]], added in
+ *     ascending j in fp64 -- the bits of a sequential loop) / n_K; tail@K = (positions j < n_K with a
+ *     non-zero tail byte, an integer count) / n_K, one division.
+ *   out_stats double [n_lists][n_cutoffs][2] = (value, tail). cutoffs_host[n_cutoffs] (HOST memory):
+ *     1 <= k_1 < ... < k_m <= k, 1 <= m <= 8.
+ *   out_flags[i] bit 0: n_K = 0 at some cutoff (an empty list); bit 1 (DCUE_LIST_FLAG_BAD_INDEX): an
+ *     entry L[j], j < c, lies outside [0, n_cand) -- each entry is range-checked before it addresses
+ *     anything. A flagged list's values are 0 and it is left out of the means.
+ * dcue_list_item_stats_mean: out_mean [n_cutoffs][2] = the arithmetic mean over the lists with flags == 0,
+ *   *out_n_evaluated their number (means 0 where it is 0), summed in dcue_topk_metrics_mean's fixed order,
+ *   which depends on n_lists and n_cutoffs alone.
+ * Exposure Gini. exposure int32 [n_cutoffs][n_cand]: dcue_topk_metrics' exposure counts. For cutoff i, over
+ *   the n candidates with a non-zero byte in cand_mask (uint8 [n_cand]; null: all n_cand): x_c = the sum
+ *   of exposure[i'][c] over i' <= i (the cumulation out_coverage uses), x_(1) <= ... <= x_(n) ascending,
+ *     out_gini[i] = double(sum_j (2j - n - 1) x_(j)) / double(n * sum_c x_c),   out_total[i] = sum_c x_c,
+ *   and out_gini[i] = 0 where n = 0 or the total is 0. Numerator and denominator are exact integers
+ *   (a histogram over the values by integer atomics and one scan), so the result is one fp64 division,
+ *   independent of launch shape and arrival order.
+ *   Workspace: a 64-byte header and one uint32 histogram bin per value 0..n_lists_max and cutoff;
+ *   dcue_exposure_gini_workspace_bytes is a host computation. n_lists_max: the lists that added to
+ *   `exposure` (a list names a candidate once, so no count exceeds it). dcue_exposure_gini reads the
+ *   number of bins back from ws_bytes: (ws_bytes - 64) / 4 / n_cutoffs. A count outside the histogram
+ *   (or a negative one) is never used as an address: that cutoff gets out_total -1 and out_gini 0, and
+ *   so does one whose n * total reaches 2^53.
+ *   Refused with DCUE_ERR_UNSUPPORTED, on the host: n_cand * n_lists_max * DCUE_TOPK_MAX_K >= 2^53, the
+ *   largest n * total lists of at most DCUE_TOPK_MAX_K entries can produce -- n_cand and ws_bytes (the bins
+ *   it holds, less one, as n_lists_max) are the arguments the bound is taken from.
+ * dcue_list_item_stats* are one launch each, no workspace; dcue_exposure_gini is one memset and two
+ * launches. All are asynchronous on `stream`. Every argument is validated on the host before the first
+ * device call, each refusal with a dcue_last_error text (DCUE_ERR_INVALID: a null required pointer, k
+ * outside 1..DCUE_TOPK_MAX_K, bad cutoffs, n_cutoffs outside 1..8, n_cand <= 0, n_lists < 0, n_lists_max
+ * < 0; DCUE_ERR_UNSUPPORTED: n_cand beyond dcue_topk's bound, the 2^53 rule; DCUE_ERR_WORKSPACE: no room
+ * for two bins per cutoff). n_lists == 0 is DCUE_OK (the mean call then writes zeros). */
+#define DCUE_ITEM_FLAG_EMPTY 1 /* bit 1: DCUE_LIST_FLAG_BAD_INDEX */
+#define DCUE_ITEM_N_STATS 2    /* value, tail */
+int dcue_list_item_stats(const int32_t* idx, const int32_t* count, int32_t n_lists, int32_t k,
+                         const double* item_value, const uint8_t* item_tail, int64_t n_cand,
+                         const int32_t* cutoffs_host, int32_t n_cutoffs, double* out_stats /* [n][m][2] */,
+                         int32_t* out_flags, void* stream);
+int dcue_list_item_stats_mean(const double* stats, const int32_t* flags, int32_t n_lists, int32_t n_cutoffs,
+                              double* out_mean /* [m][2] */, int32_t* out_n_evaluated, void* stream);
+int dcue_exposure_gini_workspace_bytes(int64_t n_cand, int32_t n_cutoffs, int64_t n_lists_max, size_t* bytes_host);
+int dcue_exposure_gini(const int32_t* exposure, const uint8_t* cand_mask, int64_t n_cand, int32_t n_cutoffs,
+                       void* ws, size_t ws_bytes, double* out_gini, int64_t* out_total, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,10 @@ this is that driver for the MI355X build:
   python train_dcue.py ... --artists artists.csv --recommend-k 10 --recommend-out recs.csv --recommend-artists-out a.csv
                                                   # + each user's 10 best artists
   python train_dcue.py ... --eval-k 10,50 --eval-out metrics.json --eval-ild --eval-diversity 0.7
+  python train_dcue.py ... --recommend-k 10 --recommend-out recs.csv --recommend-popularity -0.2
+                                                  # demote the hits (--popularity counts.csv: whose counts)
+  python train_dcue.py ... --eval-k 10,50 --eval-out metrics.json --eval-novelty --eval-popularity -0.2
+                                                  # + novelty@K, tail@K, gini@K of the demoted lists
                                                   # + intra-list diversity, of the MMR re-ranked lists
 
 triplets: (user_id, song_id, score) by column position (datasets/dcuedataset.py:229,238);
@@ -104,6 +108,17 @@ def parse(argv=None):
                     help="--eval-k also reports ild@K, the lists' mean intra-list diversity")
     ap.add_argument("--eval-diversity", type=float, metavar="L",
                     help="--eval-k scores the MMR re-ranked lists (lambda = L) instead of the plain ranking")
+    ap.add_argument("--popularity", metavar="FILE.csv",
+                    help="song_id, count: the play counts behind --recommend-popularity / --eval-popularity / "
+                         "--eval-novelty (DCUE.set_popularity); default: the training data's per-song user counts")
+    ap.add_argument("--recommend-popularity", type=float, metavar="B",
+                    help="the --recommend-k / --recommend-for lists rank by cosine + B * (the song's scaled "
+                         "log-popularity in [0, 1]): B < 0 demotes the hits, B > 0 promotes them "
+                         "(DCUE.recommend(popularity=B)); default: the plain ranking")
+    ap.add_argument("--eval-popularity", type=float, metavar="B",
+                    help="--eval-k scores the lists --recommend-popularity B would serve")
+    ap.add_argument("--eval-novelty", action="store_true",
+                    help="--eval-k also reports novelty@K, tail@K and gini@K")
     ap.add_argument("--crop", choices=["load", "epoch"], default="load",
                     help="DCUE(crop=...): 'load' cuts each track's 131-frame window once, when the catalogue is "
                          "loaded; 'epoch' keeps the full-length tracks in HBM and cuts a fresh random window of "
@@ -183,6 +198,15 @@ def parse(argv=None):
         ap.error("--recommend-reasons must be in 1..8, got %r" % args.recommend_reasons)
     if (args.eval_ild or args.eval_diversity is not None) and not args.eval_k:
         ap.error("--eval-ild / --eval-diversity need --eval-k")
+    if args.recommend_popularity is not None and args.recommend_k <= 0:
+        ap.error("--recommend-popularity needs --recommend-k")
+    if (args.eval_popularity is not None or args.eval_novelty) and not args.eval_k:
+        ap.error("--eval-popularity / --eval-novelty need --eval-k")
+    if args.popularity and args.recommend_popularity is None and args.eval_popularity is None and not args.eval_novelty:
+        ap.error("--popularity goes with --recommend-popularity, --eval-popularity or --eval-novelty")
+    for name in ("recommend_popularity", "eval_popularity"):
+        if getattr(args, name) is not None and not np.isfinite(getattr(args, name)):
+            ap.error("--%s takes a finite number, got %r" % (name.replace("_", "-"), getattr(args, name)))
     for name in ("recommend_diversity", "eval_diversity"):
         lam = getattr(args, name)
         if lam is not None and not 0.0 <= lam <= 1.0:
@@ -268,6 +292,14 @@ def main(argv=None):
         names = pd.read_csv(args.artists, dtype=str)
         dcue.set_artists(dict(zip(names["song_id"], names["artist"])))
         artist_kw = dict(max_per_artist=args.recommend_max_per_artist, new_artists=args.recommend_new_artists)
+    if args.recommend_popularity is not None or args.eval_popularity is not None or args.eval_novelty:
+        counts = None
+        if args.popularity:
+            table = pd.read_csv(args.popularity, dtype={"song_id": str})
+            counts = {s: int(c) for s, c in zip(table["song_id"], table["count"])}
+        dcue.set_popularity(counts)
+    if args.recommend_popularity is not None:
+        artist_kw = dict(artist_kw, popularity=args.recommend_popularity)
     if args.recommend_k > 0 and args.recommend_out:
         if args.recommend_for:
             new = pd.read_csv(args.recommend_for, dtype=str)
@@ -282,30 +314,38 @@ def main(argv=None):
                                   reasons=args.recommend_reasons, reasons_path=args.reasons_out, **artist_kw)
         if args.recommend_artists_out:
             write_artists(dcue, list(train.uniq_users), args.recommend_k, args.recommend_artists_out,
-                          new_artists=args.recommend_new_artists)
+                          new_artists=args.recommend_new_artists, popularity=args.recommend_popularity)
     if args.eval_k:
         write_metrics(dcue, val, test, args.eval_k, args.eval_out, diversity=args.eval_diversity, ild=args.eval_ild,
-                      artists=args.eval_artists, max_per_artist=args.recommend_max_per_artist if args.eval_artists else None)
+                      artists=args.eval_artists, max_per_artist=args.recommend_max_per_artist if args.eval_artists else None,
+                      popularity=args.eval_popularity, novelty=args.eval_novelty)
     return dcue
 
 
-def write_artists(dcue, users, k, path, new_artists=False):
+def write_artists(dcue, users, k, path, new_artists=False, popularity=None):
     """The best-by-validation factors' k best artists per user (DCUE.recommend_artists), one CSV row per
     (user, rank): the artist, and the song of theirs that ranks highest for the user with its score."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
-    lists = dcue.recommend_artists(users, k=k, new_artists=new_artists)
+    pkw = {} if popularity is None else dict(popularity=popularity)
+    lists = dcue.recommend_artists(users, k=k, new_artists=new_artists, **pkw)
     rows = [(u, r + 1, artist, song, score) for u, lst in zip(users, lists) for r, (artist, song, score) in enumerate(lst)]
     pd.DataFrame(rows, columns=["user_id", "rank", "artist", "song_id", "score"]).to_csv(path, index=False)
 
 
-def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False, artists=False, max_per_artist=None):
+def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False, artists=False, max_per_artist=None,
+                  popularity=None, novelty=False):
     """The best-by-validation factors' top-K ranking metrics over the val and the test split's songs
     (diversity: of the MMR re-ranked lists; ild: with their intra-list diversity; artists: with the
-    artist numbers; max_per_artist: of the capped lists)."""
+    artist numbers; max_per_artist: of the capped lists; popularity: of the lists that prior serves; novelty:
+    with novelty@K, tail@K and gini@K)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
     kw = dict(artists=True, max_per_artist=max_per_artist) if artists else {}
+    if popularity is not None:
+        kw["popularity"] = popularity
+    if novelty:
+        kw["novelty"] = True
     res = {"val": dcue.evaluate_topk(val, ks=ks, diversity=diversity, ild=ild, **kw),
            "test": dcue.evaluate_topk(test, ks=ks, diversity=diversity, ild=ild, **kw)}
     with open(path, "w") as f:
@@ -314,17 +354,19 @@ def write_metrics(dcue, val, test, ks, path, diversity=None, ild=False, artists=
 
 
 def write_recommendations(dcue, users, k, path, histories=None, seed=0, diversity=None, pool=None, reasons=None,
-                          reasons_path=None, max_per_artist=None, new_artists=False):
+                          reasons_path=None, max_per_artist=None, new_artists=False, popularity=None):
     """The best-by-validation factors' top-k unseen songs per user, one CSV row per (user, rank).
     histories: {user_id: [song_id, ...]} of users outside the training set (DCUE.recommend_for).
     diversity / pool: MMR re-ranked lists (DCUE.recommend). reasons / reasons_path: also each pick's
     `reasons` nearest history songs (DCUE.explain / explain_for), one row per (user, rank, reason_rank).
-    max_per_artist / new_artists: as DCUE.recommend (none without artists: today's calls)."""
+    max_per_artist / new_artists / popularity: as DCUE.recommend (none given: today's calls)."""
     if dcue.best_user_factors is not None:
         dcue.insert_best_factors()
     akw = {}
     if max_per_artist is not None or new_artists:
         akw = dict(max_per_artist=max_per_artist, new_artists=new_artists)
+    if popularity is not None:
+        akw["popularity"] = popularity
     if reasons is not None:
         if histories is not None:
             lists = dcue.explain_for([histories[u] for u in users], k=k, reasons=reasons, seed=seed,
